@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: RPY-wall M.f matvecs/s on MI355X (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, the declared pre-warm, W warm-up steps, K timed steps, the output of
+the last step written to DIR/velocity.npy if --dump-outputs is given, and one line with `value`, `ms_per_step`, the
+roofline from the HIP events of the timed steps (`issue` null) and `build`.  --full adds `value_unprimed`, the live
+issue ceiling of `roofline.issue` and every extra listed below (host_surface onwards).
 
 N > 1 launched plainly (no torchrun environment): this process spawns the N ranks itself -- child processes with
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, started BEFORE anything here touches the
@@ -107,6 +112,11 @@ def parse_args():
                        "(the watchdog then prints the line with what exists and ends the run); 0 disables")
   ap.add_argument("--no-host-surface", action="store_true",
                   help="skip the host_surface extra (profiling runs: the last K dispatches of the trace are then the timed ones)")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure everything beside the headline: value_unprimed, roofline.issue and every extra (the "
+                       "--no-* flags above then pick among them); without it the run times the headline only")
+  ap.add_argument("--dump-outputs", metavar="DIR",
+                  help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
   return ap.parse_args()
 
 
@@ -250,11 +260,11 @@ def committed_traffic(N, sym):
   return None, {"measured_in_this_run": False, "source": None}
 
 
-def load_isa():
+def load_isa(regenerate=True):
   """Instruction mix of the pair loops of THIS build (tools/isa_stats.py; hashed against csrc/), or None."""
   try:
     import isa_stats
-    return isa_stats.load()
+    return isa_stats.load(regenerate=regenerate)
   except Exception:
     return None
 
@@ -499,15 +509,19 @@ def rank_main(args):
   N = args.blobs
   _inject("headline", rank)       # test hook: a rank that never produces its headline (cut by the whole-run budget)
   res = run_config(torch, dist, sm, backend, N, args.steps, args.warmup, world, rank, device, "pair", args.prewarm_ms,
-                   unprimed=True)
+                   unprimed=args.full)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, res["out"])
   ms_per_step = 1e3 * res["dt"] / args.steps
   value = args.steps / res["dt"]
   sym = res["launch"]["chunks"] == 0
-  issue_peak = backend.ctx.ubench_fp64_issue(40)      # same process, clocks still primed by the timed loop
-  if world > 1:
-    t = torch.tensor([issue_peak], dtype=torch.float64, device=device)
-    dist.all_reduce(t, op=dist.ReduceOp.MIN)
-    issue_peak = float(t.item())
+  issue_peak = None
+  if args.full:
+    issue_peak = backend.ctx.ubench_fp64_issue(40)      # same process, clocks still primed by the timed loop
+    if world > 1:
+      t = torch.tensor([issue_peak], dtype=torch.float64, device=device)
+      dist.all_reduce(t, op=dist.ReduceOp.MIN)
+      issue_peak = float(t.item())
 
   # ---- roofline of the dominant kernel: one rank's launch covers 1/world of the pairs -------------------------
   kern_s = res["kern_ms"] * 1e-3
@@ -515,7 +529,7 @@ def rank_main(args):
   alg_tf = FLOPS_PER_PAIR["tt_wall"] * pairs_ordered / kern_s / 1e12
   alg_bytes = 48.0 * N + 24.0 * (res["n_local"] if world == 1 else N)
   traffic, traffic_src = committed_traffic(N, sym) if world == 1 else (None, {"measured_in_this_run": False, "source": None})
-  isa = load_isa()
+  isa = load_isa(regenerate=args.full)     # a plain run never compiles: build() wrote the count for these sources
   executed, issue = executed_views(isa, sym, N, world, res["n_local"], kern_s, issue_peak, key=isa_key(res["path"]))
   if executed is None:
     # no instruction count for this build (tools/isa_stats.py needs hipcc): the utilisation cannot be priced; say so
@@ -585,8 +599,9 @@ def rank_main(args):
 
   def stage(key, expect_s, fn, single_rank_only=False):
     """One extra.  world == 1: an exception is recorded and the run goes on.  world > 1: the failing rank raises the
-    abort marker and every rank leaves within a second -- no rank ever skips ahead of the others' collectives."""
-    if single_rank_only and not (rank == 0 and world == 1):
+    abort marker and every rank leaves within a second -- no rank ever skips ahead of the others' collectives.  Only
+    with --full: a plain run stops at the headline."""
+    if not args.full or (single_rank_only and not (rank == 0 and world == 1)):
       return
     if not guard.begin(key, expect_s, torch, dist, device):
       line[key] = {"skipped": "would not fit the wall-clock budget (%.0f s of %.0f s used)" % (guard.elapsed(), guard.budget)}
@@ -1128,7 +1143,7 @@ def rank_main(args):
   if not args.no_sweep:
     stage("config5_multiblob_brownian", 60, config5_multiblob)
 
-  if not args.no_host_surface and rank == 0 and world == 1:
+  if args.full and not args.no_host_surface and rank == 0 and world == 1:
     # Last of all: first contact of the one-process engine with real peer devices happens in a child process, after
     # every other number exists; the line as it stands goes to stderr and to the headline file first.
     guard.publish_headline(line, full=True)
@@ -1149,6 +1164,20 @@ def build_record():
       return json.load(fh)
   except (OSError, ValueError):
     return {"mode": "unknown (no build record next to the library)"}
+
+
+DUMP_MAX_ROWS = 1 << 21       # 48 MiB of fp64 (x, y, z) rows: the cap of --dump-outputs is 64 MB in all
+
+
+def dump_outputs(out_dir, out):
+  """--dump-outputs: what a caller of the timed path receives from its last step, u = M_tt f as (N_blobs, 3) fp64, in
+  DIR/velocity.npy.  The inputs are seeded (d2_cloud), so two builds run with the same arguments can be compared
+  output for output.  Above DUMP_MAX_ROWS blobs the file holds a fixed sample: the rows of a seeded choice, sorted."""
+  u = out.cpu().numpy().reshape(-1, 3)
+  if len(u) > DUMP_MAX_ROWS:
+    u = u[np.sort(np.random.RandomState(0).choice(len(u), DUMP_MAX_ROWS, replace=False))]
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, "velocity.npy"), u)
 
 
 def main():

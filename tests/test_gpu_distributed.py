@@ -104,8 +104,8 @@ def _say(res, line, took):
 def test_bench_rank_failure_in_an_extra_ends_the_run_within_seconds_and_keeps_the_headline():
   """One rank raises inside a multi-rank extra (whose other ranks are inside collectives): the run must end within
   seconds, with the headline on the line and the failure recorded -- never a hang."""
-  res, line, took = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--prewarm-ms", "20", "--no-cpu", "--no-host-surface"],
-                           {"RMB_BENCH_INJECT": "fail:1:decompositions"}, 400)
+  res, line, took = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--prewarm-ms", "20", "--no-cpu", "--no-host-surface",
+                            "--full"], {"RMB_BENCH_INJECT": "fail:1:decompositions"}, 400)
   say = _say(res, line, took)
   assert line is not None, say
   assert line.get("value", 0) > 0 and line.get("n_gpus") == 2, say
@@ -119,7 +119,7 @@ def test_bench_hang_in_an_extra_is_cut_at_its_stage_limit():
   so independent of how long interpreter start, rendezvous and the headline took on this box (the round-4 driver run
   lost the headline to a 45 s whole-run budget) -- rank 0 prints the line with what exists and all ranks leave."""
   res, line, took = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--prewarm-ms", "20", "--no-cpu", "--no-host-surface",
-                            "--stage-limit-s", "8"], {"RMB_BENCH_INJECT": "hang:1:decompositions"}, 400)
+                            "--stage-limit-s", "8", "--full"], {"RMB_BENCH_INJECT": "hang:1:decompositions"}, 400)
   say = _say(res, line, took)
   assert line is not None, say
   assert line.get("value", 0) > 0, say
@@ -139,7 +139,7 @@ def test_bench_hang_before_the_headline_is_cut_at_the_wall_clock_budget():
 
 @pytest.mark.bench_harness
 def test_bench_single_rank_extra_failure_is_recorded_and_the_run_goes_on():
-  res, line, took = _bench(["--steps", "5", "--warmup", "2", "--prewarm-ms", "20", "--no-cpu", "--no-sweep"],
+  res, line, took = _bench(["--steps", "5", "--warmup", "2", "--prewarm-ms", "20", "--no-cpu", "--no-sweep", "--full"],
                            {"RMB_BENCH_INJECT": "fail:0:host_surface"}, 400)
   say = _say(res, line, took)
   assert res.returncode == 0 and line is not None, say
