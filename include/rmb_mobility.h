@@ -517,6 +517,42 @@ int rmb_double_layer_device(rmb_ctx* ctx, long ns, const double* src_dev, long n
                             const double* normals_dev, const double* vector_dev, const double* weights_dev, int wall,
                             double blob_radius, double* out_dev);
 
+/* ---- Laplace layer operators of phoretic bodies -------------------------------------------------------------------
+ * Laplace_kernels/Laplace_kernels_numba.py.  Nodes x (n x 3), quadrature weights w, unit normals n, a field f per
+ * node; every operator is 1/(4 pi) sum_j w_j f_j K(x_i - x_j).  wall = 1 adds the image of a no-slip wall at z = 0:
+ * source (x, y, -z), normal (n_x, n_y, -n_z), kept for j == i.  The self operators skip the free-space term of
+ * j == i by index, the source -> target ones every pair with |r| < 1e-12.  Plain positions (no height clamp), no
+ * periodic images.  Atomic-free, bit-reproducible; the host variants run synchronously on the default context.
+ *
+ * rmb_laplace_single_layer:          out[n]    S[f]_i = 1/(4 pi) sum_j w_j f_j / |r_ij|                 (:12)
+ * rmb_laplace_double_layer:          out[n]    D[f]_i = 1/(4 pi) sum_j w_j f_j (r_ij . n_j) / |r_ij|^3   (:68)
+ * rmb_laplace_deriv_double_layer:    out[3n]   G[f]_i = 1/(4 pi) sum_j w_j f_j (I - 3 r r^T/r^2) n_j / r^3  (:138)
+ * rmb_laplace_dipole:                out[3n]   P[f]_i = 1/(4 pi) sum_j w_j f_j r_ij / |r_ij|^3          (:254)
+ * rmb_laplace_single_layer_source_target, rmb_laplace_double_layer_source_target: out[nt], S / D from ns sources
+ *   to nt targets                                                                                        (:329, :398)
+ *
+ * Device sweeps of the concentration solve (phoretic slip), sources = targets = the n nodes, on the context's stream;
+ * out must not alias an input:
+ * rmb_laplace_operator_device:  out[n]  = alpha p_i - D[p]_i + S[q]_i   in one pass.  p or q may be NULL (that term is
+ *   absent and not computed; alpha applies to p); normals may be NULL when p is.
+ * rmb_laplace_gradient_device:  out[3n] = 2 G[p]_i - 2 P[q]_i   in one pass; p or q may be NULL likewise. */
+int rmb_laplace_single_layer(long n, const double* r, const double* field, const double* weights, int wall, double* out);
+int rmb_laplace_double_layer(long n, const double* r, const double* field, const double* weights, const double* normals,
+                             int wall, double* out);
+int rmb_laplace_deriv_double_layer(long n, const double* r, const double* field, const double* weights,
+                                   const double* normals, int wall, double* out);
+int rmb_laplace_dipole(long n, const double* r, const double* field, const double* weights, int wall, double* out);
+int rmb_laplace_single_layer_source_target(long ns, const double* src, long nt, const double* tgt, const double* field,
+                                           const double* weights, int wall, double* out);
+int rmb_laplace_double_layer_source_target(long ns, const double* src, long nt, const double* tgt, const double* field,
+                                           const double* weights, const double* normals, int wall, double* out);
+int rmb_laplace_operator_device(rmb_ctx* ctx, long n, const double* r_dev, const double* normals_dev,
+                                const double* weights_dev, const double* p_dev, const double* q_dev, double alpha, int wall,
+                                double* out_dev);
+int rmb_laplace_gradient_device(rmb_ctx* ctx, long n, const double* r_dev, const double* normals_dev,
+                                const double* weights_dev, const double* p_dev, const double* q_dev, int wall,
+                                double* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,15 @@ SYMBOLS = {
                                         ctypes.c_double, _vp]),
     "rmb_double_layer_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_int,
                                                ctypes.c_double, _vp]),
+    "rmb_laplace_single_layer": (ctypes.c_int, [ctypes.c_long, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "rmb_laplace_double_layer": (ctypes.c_int, [ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "rmb_laplace_deriv_double_layer": (ctypes.c_int, [ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "rmb_laplace_dipole": (ctypes.c_int, [ctypes.c_long, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "rmb_laplace_single_layer_source_target": (ctypes.c_int, [ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "rmb_laplace_double_layer_source_target": (ctypes.c_int, [ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                              _vp]),
+    "rmb_laplace_operator_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, _vp]),
+    "rmb_laplace_gradient_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
 }
 
 

@@ -394,6 +394,43 @@ class MobilityContext(object):
                                                    float(eta), ctypes.c_void_p(out.data_ptr())))
     return out
 
+  def _laplace_args(self, r, weights, p, q, normals):
+    import torch
+    n = r.numel() // 3
+    for name, t, size in (("r", r, 3 * n), ("weights", weights, n), ("p", p, n), ("q", q, n), ("normals", normals, 3 * n)):
+      if t is not None and (not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != size):
+        raise ValueError("%s must be a contiguous CUDA float64 tensor with %d entries" % (name, size))
+    if p is None and q is None:
+      raise ValueError("p and q are both None")
+    if p is not None and normals is None:
+      raise ValueError("the p term needs the normals")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    return n, ptr(r), ptr(normals), ptr(weights), ptr(p), ptr(q)
+
+  def laplace_operator_device(self, r, weights, p=None, q=None, normals=None, alpha=0.0, wall=False, out=None):
+    """out = alpha p - D[p] + S[q] on the nodes r (3n tensor; Laplace layer operators, rmb_laplace_operator_device) in one
+    pass; a None field drops its term (alpha goes with p).  Independent of the bound configuration."""
+    import torch
+    n, rp, np_, wp, pp, qp = self._laplace_args(r, weights, p, q, normals)
+    if out is None:
+      out = torch.empty(n, dtype=torch.float64, device=r.device)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_laplace_operator_device(self._h, n, rp, np_, wp, pp, qp, float(alpha), 1 if wall else 0,
+                                                     ctypes.c_void_p(out.data_ptr())))
+    return out
+
+  def laplace_gradient_device(self, r, weights, p=None, q=None, normals=None, wall=False, out=None):
+    """out (3n) = 2 G[p] - 2 P[q] on the nodes r: gradient of the double layer and dipole (rmb_laplace_gradient_device) in
+    one pass; a None field drops its term."""
+    import torch
+    n, rp, np_, wp, pp, qp = self._laplace_args(r, weights, p, q, normals)
+    if out is None:
+      out = torch.empty(3 * n, dtype=torch.float64, device=r.device)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_laplace_gradient_device(self._h, n, rp, np_, wp, pp, qp, 1 if wall else 0,
+                                                     ctypes.c_void_p(out.data_ptr())))
+    return out
+
   def blob_blob_force(self, repulsion_strength, debye_length, blob_radius):
     out = np.empty(3 * self.n_targets)
     _lib.check(self._lib.rmb_blob_blob_force(self._h, float(repulsion_strength), float(debye_length),

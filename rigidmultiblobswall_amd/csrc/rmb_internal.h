@@ -17,6 +17,8 @@
 //   rmb_rigid.hip    per-body geometry (positions, K) and the per-body factors of the block-diagonal preconditioner
 //   rmb_krylov.hip   O(N) helpers of the rigid-body solve: batched 2 x 2 block product, fused Gram-Schmidt step
 //   rmb_gmres.hip    the whole right-preconditioned GMRES of the rigid-body problem as one call (host loop native too)
+//   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
+//                    points and the two fused device sweeps of the concentration solve
 #pragma once
 #include "../../include/rmb_mobility.h"
 

@@ -80,3 +80,24 @@ def uniform_vertices(coor, blob_radius, path):
                        "radii (the reference's radii_* modes) are not run by the time steppers"
                        % (path, rad.min(), rad.max(), blob_radius))
   return coor[:, :3]
+
+
+def phoretic(read):
+  """True when a `structure` line of the deck names a .Laplace file (phoretic bodies, multi_bodies.py:1175-1217).
+  ValueError for what the phoretic slip here does not run: structures without a .Laplace file next to ones with it
+  (the reference's calc_slip fails on them: `b.normals` is missing), periodic images (the Laplace operators have none)
+  and the roller schemes."""
+  flags = [any(f.endswith(".Laplace") for f in s[2:]) for s in read.structures]
+  if not any(flags):
+    return False
+  if not all(flags):
+    missing = [s[0] for s, f in zip(read.structures, flags) if not f]
+    raise ValueError("phoretic deck: every structure needs a .Laplace file (the reference's calc_slip reads normals and "
+                     "rates of every body); missing for %s" % ", ".join(missing))
+  L = np.asarray(read.periodic_length, dtype=np.float64).reshape(-1)
+  if np.any(L != 0):
+    raise ValueError("phoretic deck with periodic_length %s: the Laplace layer operators have no periodic images"
+                     % " ".join("%g" % x for x in L))
+  if "rollers" in read.scheme:
+    raise ValueError("phoretic deck with scheme %s: the roller schemes do not run the phoretic slip" % read.scheme)
+  return True

@@ -13,6 +13,12 @@ def _vec(s):
   return np.array(s.split(), dtype=np.float64)
 
 
+def _background(s):
+  """background_Laplace: up to 9 values, zero-padded to 9 (read_input.py:100-101)."""
+  from .laplace import background_vector
+  return background_vector(_vec(s))
+
+
 # option -> (attribute name, converter, default)       defaults as read_input.py:48-102
 _OPTIONS = {
     "n_steps": ("n_steps", int, 0),
@@ -61,6 +67,7 @@ _OPTIONS = {
     "zmax": ("zmax", float, 1e7),
     "domType": ("domType", str, "RPB"),
     "diffusion_coefficient": ("diffusion_coefficient", float, 1.0),
+    "background_Laplace": ("background_Laplace", _background, np.zeros(9)),
 }
 
 

@@ -174,6 +174,9 @@ class RigidIntegrator(object):
     self._precision = value
     self.susp.ctx.set_option("precision", 32 if value == 'single' else 64)
   def close(self):
+    close_slip = getattr(self.calc_slip, "close", None)     # laplace.PhoreticSlip may own a context
+    if close_slip is not None:
+      close_slip()
     self.susp.close()
 
   # ---- plumbing -------------------------------------------------------------------------------------
@@ -772,11 +775,13 @@ class RigidIntegrator(object):
 
 def bodies_from_input(read):
   """Bodies of a deck as multi_bodies/multi_bodies.py:1160-1212 creates them: every `structure` line = vertex file +
-  clones file (+ optional .slip file with one body-frame slip per blob).  Returns a dict with one reference
-  configuration and one body-frame slip array per body, stacked locations / quaternions, and bodies per structure."""
+  clones file (+ optional .slip file with one body-frame slip per blob, + optional .Laplace file with one row of
+  phoretic data per blob).  Returns a dict with one reference configuration and one body-frame slip array per body,
+  stacked locations / quaternions, bodies per structure, and the stacked .Laplace rows (None without .Laplace files)."""
   from . import deck_modes
   from . import structures as st
-  refs, locs, quats, slips, body_types = [], [], [], [], []
+  from .laplace import read_laplace_file
+  refs, locs, quats, slips, body_types, laplace = [], [], [], [], [], []
   any_slip = False
   if read.articulated:
     raise ValueError("articulated bodies are not supported")
@@ -784,14 +789,18 @@ def bodies_from_input(read):
   for sid, structure in enumerate(read.structures):
     ref = deck_modes.uniform_vertices(st.read_vertex_file(read.resolve(structure[0])), read.blob_radius, structure[0])
     n, loc, quat = st.read_clones_file(read.resolve(structure[1]))
-    slip = None
+    slip = lap = None
     for extra in structure[2:]:
       if extra.endswith(".slip"):
         slip = st.read_slip_file(read.resolve(extra))[:len(ref)]
         any_slip = True
+      elif extra.endswith(".Laplace"):
+        lap = read_laplace_file(read.resolve(extra), len(ref))
     for k in range(n):
       refs.append(ref)
       slips.append(slip if slip is not None else np.zeros((len(ref), 3)))
+      if lap is not None:
+        laplace.append(lap)
       prescribed.append(sid >= read.num_free_bodies)      # `obstacle` lines follow the `structure` lines
     locs.append(loc)
     quats.append(quat)
@@ -800,13 +809,15 @@ def bodies_from_input(read):
     raise ValueError("input deck lists no structure")
   return dict(refs=refs, locations=np.concatenate(locs), quaternions=np.concatenate(quats),
               slips=np.concatenate(slips) if any_slip else None, body_types=body_types,
-              structures_ID=list(read.structures_ID), prescribed=np.array(prescribed, dtype=bool))
+              structures_ID=list(read.structures_ID), prescribed=np.array(prescribed, dtype=bool),
+              laplace=np.concatenate(laplace) if laplace else None)
 
 
 def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   """Integrator wired from a ReadInput deck as multi_bodies/multi_bodies.py:1319-1393 wires QuaternionIntegrator."""
   from . import deck_modes
   deck_modes.validate(read, uses_dense_blocks=True)     # ValueError for modes this engine does not run
+  phoretic = deck_modes.phoretic(read)                  # ValueError for phoretic modes this engine does not run
   b = bodies_from_input(read)
   refs, body_types, any_slip = b["refs"], b["body_types"], b["slips"] is not None
   if rng is None:
@@ -826,6 +837,11 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
     integ.debye_length = read.debye_length
   if any_slip:
     integ.slip_body_frame = torch.as_tensor(b["slips"], device=integ.device)
+  if phoretic:
+    from .laplace import PhoreticSlip
+    integ.calc_slip = PhoreticSlip(integ.susp, b["laplace"], background=read.background_Laplace,
+                                   diffusion_coefficient=read.diffusion_coefficient, tolerance=read.solver_tolerance,
+                                   wall=read.domain == "single_wall", slip_body_frame=integ.slip_body_frame)
   integ.body_types = body_types
   integ.structures_ID = b["structures_ID"]
   return integ

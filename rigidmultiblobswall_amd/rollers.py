@@ -607,6 +607,7 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   from . import deck_modes
   from . import structures as st
   deck_modes.validate(read, uses_dense_blocks=False)    # ValueError for modes this engine does not run
+  deck_modes.phoretic(read)                             # ValueError for .Laplace files
   locations = []
   body_types = []
   for vertex_file, clones_file in [s[:2] for s in read.structures]:

@@ -1,0 +1,132 @@
+"""Phoretic bodies without a GPU: .Laplace files, background_Laplace, the deck checks, and the numpy restatement of the
+six Laplace layer operators against the reference's own values (tests/golden/g12_laplace_operators.npz)."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, load_golden
+import _laplace_numpy as lapnp
+
+DECK = """scheme                                   {scheme}
+mobility_blobs_implementation            python
+mobility_vector_prod_implementation      python
+domain                                   single_wall
+blob_radius                              0.25
+{extra}
+output_name                              run
+{structures}
+"""
+VERTEX = np.array([[0.5, 0.0, 0.0], [-0.5, 0.0, 0.0], [0.0, 0.5, 0.0], [0.0, -0.5, 0.0]])
+
+
+def _write(tmp_path, structures, scheme="deterministic_forward_euler", extra="", laplace_rows=None):
+  d = str(tmp_path)
+  with open(os.path.join(d, "b.vertex"), "w") as fh:
+    fh.write("%d\n" % len(VERTEX))
+    for x in VERTEX:
+      fh.write("%.17g %.17g %.17g\n" % tuple(x))
+  with open(os.path.join(d, "b.clones"), "w") as fh:
+    fh.write("2\n0 0 2 1 0 0 0\n3 0 2 1 0 0 0\n")
+  rows = laplace_rows
+  if rows is None:
+    rows = np.column_stack([VERTEX / 0.5, np.full(4, 0.1), np.full(4, 1.0), np.full(4, 0.5), np.full(4, 0.7)])
+  with open(os.path.join(d, "b.Laplace"), "w") as fh:
+    fh.write("# normals, reaction rate, emitting rate, surface mobility, weights\n")
+    for x in rows:
+      fh.write(" ".join("%.17g" % v for v in x) + "\n")
+  deck = os.path.join(d, "deck.dat")
+  with open(deck, "w") as fh:
+    fh.write(DECK.format(scheme=scheme, extra=extra, structures="\n".join(structures)))
+  from rigidmultiblobswall_amd.read_input import ReadInput
+  return ReadInput(deck)
+
+
+def test_laplace_file_is_read_per_blob(tmp_path):
+  from rigidmultiblobswall_amd import rigid_integrator
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace"])
+  b = rigid_integrator.bodies_from_input(read)
+  assert b["laplace"].shape == (8, 7)
+  np.testing.assert_array_equal(b["laplace"][:4], b["laplace"][4:])
+  assert b["laplace"][0, 6] == 0.7 and b["laplace"][0, 3] == 0.1
+
+
+def test_laplace_file_row_count_must_match_the_vertex_file(tmp_path):
+  from rigidmultiblobswall_amd import rigid_integrator
+  rows = np.column_stack([np.ones((3, 3)), np.ones((3, 4))])
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace"], laplace_rows=rows)
+  with pytest.raises(ValueError, match="3 rows"):
+    rigid_integrator.bodies_from_input(read)
+
+
+def test_laplace_file_needs_seven_columns(tmp_path):
+  from rigidmultiblobswall_amd.laplace import read_laplace_file
+  p = os.path.join(str(tmp_path), "x.Laplace")
+  np.savetxt(p, np.ones((4, 6)))
+  with pytest.raises(ValueError, match="7 columns"):
+    read_laplace_file(p, 4)
+
+
+def test_background_laplace_is_padded_and_hessian_is_symmetric_traceless(tmp_path):
+  from rigidmultiblobswall_amd.laplace import background_hessian
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace"], extra="background_Laplace 1 0.5 -2")
+  np.testing.assert_array_equal(read.background_Laplace, [1, 0.5, -2, 0, 0, 0, 0, 0, 0])
+  read0 = _write(tmp_path, ["structure b.vertex b.clones"])
+  np.testing.assert_array_equal(read0.background_Laplace, np.zeros(9))
+  H = background_hessian([0, 0, 0, 0, 1.0, 2.0, 3.0, 4.0, 5.0])
+  np.testing.assert_array_equal(H, H.T)
+  assert np.trace(H) == 0.0
+  np.testing.assert_array_equal(H, [[1, 2, 3], [2, 4, 5], [3, 5, -5]])
+  with pytest.raises(ValueError):
+    _write(tmp_path, ["structure b.vertex b.clones"], extra="background_Laplace " + " ".join(["1"] * 10))
+
+
+def test_phoretic_deck_with_a_passive_structure_is_refused(tmp_path):
+  from rigidmultiblobswall_amd import deck_modes
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace", "structure b.vertex b.clones"])
+  with pytest.raises(ValueError, match="every structure needs a .Laplace"):
+    deck_modes.phoretic(read)
+
+
+def test_phoretic_deck_with_periodic_images_is_refused(tmp_path):
+  from rigidmultiblobswall_amd import deck_modes
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace"], extra="periodic_length 10 10 0")
+  with pytest.raises(ValueError, match="periodic"):
+    deck_modes.phoretic(read)
+
+
+def test_phoretic_deck_with_a_roller_scheme_is_refused(tmp_path):
+  from rigidmultiblobswall_amd import deck_modes, rollers
+  read = _write(tmp_path, ["structure b.vertex b.clones b.Laplace"], scheme="deterministic_forward_euler_rollers")
+  with pytest.raises(ValueError, match="roller"):
+    deck_modes.phoretic(read)
+  with pytest.raises(ValueError, match="roller"):
+    rollers.integrator_from_input(read, device="cpu")
+
+
+def test_deck_without_laplace_file_yields_the_same_bodies(tmp_path):
+  from rigidmultiblobswall_amd import deck_modes, rigid_integrator
+  read = _write(tmp_path, ["structure b.vertex b.clones"])
+  assert deck_modes.phoretic(read) is False
+  b = rigid_integrator.bodies_from_input(read)
+  assert b["laplace"] is None and b["slips"] is None
+  assert len(b["refs"]) == 2 and b["body_types"] == [2]
+  np.testing.assert_array_equal(b["refs"][0], VERTEX)
+  np.testing.assert_array_equal(b["locations"], [[0, 0, 2], [3, 0, 2]])
+  np.testing.assert_array_equal(b["quaternions"], [[1, 0, 0, 0], [1, 0, 0, 0]])
+  assert set(b) == {"refs", "locations", "quaternions", "slips", "body_types", "structures_ID", "prescribed", "laplace"}
+
+
+_OPS = [("single_layer", "S", False, False), ("double_layer", "D", True, False), ("deriv_double_layer", "G", True, False),
+        ("dipole", "P", False, False), ("single_layer_st", "S", False, True), ("double_layer_st", "D", True, True)]
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+@pytest.mark.parametrize("name,kind,normals,st", _OPS, ids=[o[0] for o in _OPS])
+def test_numpy_restatement_matches_reference_operators(name, kind, normals, st, wall):
+  g = load_golden(os.path.join(GOLDEN, "g12_laplace_operators.npz"))
+  out = lapnp.apply(kind, g["r"], g["field"], g["weights"], g["normals"] if normals else None, wall=wall,
+                    tgt=g["target"] if st else None)
+  ref = g["%s_wall%d" % (name, wall)]
+  assert np.all(np.isfinite(out))
+  assert np.linalg.norm(out.reshape(-1) - ref) <= 1e-13 * np.linalg.norm(ref)
