@@ -407,6 +407,12 @@ class MobilityContext(object):
     ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     return n, ptr(r), ptr(normals), ptr(weights), ptr(p), ptr(q)
 
+  @staticmethod
+  def _laplace_out(out, size):
+    """A caller's out= goes straight to the kernel: refuse any tensor it could not write in place (as matvec_device)."""
+    if not _is_torch_cuda(out) or not out.is_contiguous() or out.numel() != size:
+      raise ValueError("out must be a contiguous CUDA float64 tensor with %d entries" % size)
+
   def laplace_operator_device(self, r, weights, p=None, q=None, normals=None, alpha=0.0, wall=False, out=None):
     """out = alpha p - D[p] + S[q] on the nodes r (3n tensor; Laplace layer operators, rmb_laplace_operator_device) in one
     pass; a None field drops its term (alpha goes with p).  Independent of the bound configuration."""
@@ -414,6 +420,8 @@ class MobilityContext(object):
     n, rp, np_, wp, pp, qp = self._laplace_args(r, weights, p, q, normals)
     if out is None:
       out = torch.empty(n, dtype=torch.float64, device=r.device)
+    else:
+      self._laplace_out(out, n)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_laplace_operator_device(self._h, n, rp, np_, wp, pp, qp, float(alpha), 1 if wall else 0,
                                                      ctypes.c_void_p(out.data_ptr())))
@@ -426,6 +434,8 @@ class MobilityContext(object):
     n, rp, np_, wp, pp, qp = self._laplace_args(r, weights, p, q, normals)
     if out is None:
       out = torch.empty(3 * n, dtype=torch.float64, device=r.device)
+    else:
+      self._laplace_out(out, 3 * n)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_laplace_gradient_device(self._h, n, rp, np_, wp, pp, qp, 1 if wall else 0,
                                                      ctypes.c_void_p(out.data_ptr())))

@@ -198,3 +198,522 @@ def test_janus_step_solves_to_tolerance_and_slip_is_tangential():
   assert float(normal_part.norm()) <= 1e-12 * float(slip.norm())
   assert float(slip.norm()) > 0
   integ.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Edge shapes, forced chunks, one-hot records, identities and the dense slip: every row against the extended-precision
+# restatement (tests/_laplace_numpy.py).  Per target |hip_i - ref_i| <= 1e-13 A_i with the condition-aware scale
+# A_i = 1/(4 pi) sum_j |w_j f_j| |K|_ij (free and image terms counted separately), and relative L2 <= 1e-13 over all
+# rows; a missing, doubled or wrongly signed pair moves its target by far more than 1e-13 A_i.
+# ---------------------------------------------------------------------------------------------------------------------
+EPS = np.finfo(np.float64).eps
+TOL = 1e-13
+_WORST = {}      # what -> worst observed ratio (printed after the module: the numbers DESIGN 4 quotes)
+_KIND_FN = {"S": ("Laplace_single_layer_operator_hip", False), "D": ("Laplace_double_layer_operator_hip", True),
+            "G": ("Laplace_deriv_double_layer_operator_hip", True), "P": ("Laplace_dipole_operator_hip", False)}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+  yield
+  if _WORST:
+    print("\n[laplace] worst observed (reference %s): %s" % (lapnp.EXT_NAME, ", ".join(
+        "%s %.3g" % kv for kv in sorted(_WORST.items()))))
+
+
+def _note(what, value):
+  _WORST[what] = max(_WORST.get(what, 0.0), float(value))
+
+
+def _wrap(kind, r, f, w, nrm, wall):
+  from rigidmultiblobswall_amd import laplace
+  fn, normals = _KIND_FN[kind]
+  out = getattr(laplace, fn)(r, f, w, *((nrm,) if normals else ()), wall=wall)
+  return out.reshape(-1, 3) if kind in "GP" else out
+
+
+def _ratios(out, ref, scale):
+  """max over components of |out - ref| / scale, per target (0 / 0 = 0, x / 0 = inf)."""
+  out = np.asarray(out, dtype=np.float64).reshape(len(scale), -1)
+  d = np.abs(out.astype(lapnp.EXT) - np.asarray(ref).reshape(len(scale), -1)).astype(np.float64).max(axis=1)
+  with np.errstate(divide="ignore", invalid="ignore"):
+    return np.where(scale > 0, d / np.where(scale > 0, scale, 1.0), np.where(d > 0, np.inf, 0.0))
+
+
+def _assert_rows(out, ref, scale, what, tol=TOL):
+  """The per-target bound and the relative L2 bound over all rows."""
+  out = np.asarray(out, dtype=np.float64).reshape(len(scale), -1)
+  assert np.all(np.isfinite(out)), what
+  ratio = _ratios(out, ref, scale)
+  _note("per-target |d|/A, all rows", ratio.max())
+  assert ratio.max() <= tol, (what, float(ratio.max()), int(ratio.argmax()))
+  diff = (out.astype(lapnp.EXT) - np.asarray(ref).reshape(out.shape)).astype(np.float64)
+  nref = np.linalg.norm(np.asarray(ref, dtype=np.float64))
+  if nref == 0:
+    assert np.all(out == 0.0), what
+  else:
+    assert np.linalg.norm(diff) <= tol * nref, (what, np.linalg.norm(diff) / nref)
+
+
+_SIZES = [1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1025]
+
+
+@pytest.mark.parametrize("n", _SIZES, ids=["n%d-%s" % (n, lapnp.EXT_NAME) for n in _SIZES])
+@pytest.mark.parametrize("wall", [0, 1])
+def test_self_operators_every_row_across_tile_edges(wall, n):
+  """S, D, G, P at sizes that straddle the 64-target workgroup, the 4-wave source stride and the 512-record LDS tile."""
+  r, nrm, f, w, _ = _cloud(n, 1000 + n)
+  for kind in "SDGP":
+    nv = nrm if kind in "DG" else None
+    out = _wrap(kind, r, f, w, nv, wall)
+    ref, scale = lapnp.apply_ext(kind, r, f, w, nv, wall=wall)
+    if n == 1 and not wall:
+      assert np.all(out == 0.0), kind                       # no pair at all
+    _assert_rows(out, ref, scale, "%s n=%d wall=%d" % (kind, n, wall))
+
+
+_ST_SHAPES = [(1, 1), (1, 700), (700, 1), (3, 700), (64, 65), (257, 129), (513, 511), (5000, 64)]
+
+
+@pytest.mark.parametrize("ns,nt", _ST_SHAPES, ids=["%dx%d" % s for s in _ST_SHAPES])
+@pytest.mark.parametrize("wall", [0, 1])
+def test_source_target_shapes_and_the_coincidence_threshold(wall, ns, nt):
+  """S and D from sources to targets; a target on a source skips the free term and keeps the image, a target 0.5e-12
+  from a source skips it, one 2e-12 away keeps it (clear of the 1e-12 threshold, where r^2 < 1e-24 and r < 1e-12 may
+  round differently)."""
+  from rigidmultiblobswall_amd import laplace
+  src, nrm, f, w, _ = _cloud(ns, 2000 + ns)
+  tgt = _cloud(nt, 3000 + nt)[0] + 0.37
+  tgt[0] = src[0]                                          # coincident
+  if nt >= 3:
+    tgt[1] = src[ns - 1] + np.array([0.5e-12, 0.0, 0.0])   # skipped
+    tgt[2] = src[ns // 2] + np.array([0.0, 0.0, 2e-12])    # included
+  for kind in "SD":
+    if kind == "S":
+      out = laplace.Laplace_single_layer_operator_source_target_hip(src, tgt, f, w, wall=wall)
+    else:
+      out = laplace.Laplace_double_layer_operator_source_target_hip(src, tgt, f, w, nrm, wall=wall)
+    nv = nrm if kind == "D" else None
+    ref, scale = lapnp.apply_ext(kind, src, f, w, nv, wall=wall, tgt=tgt)
+    _assert_rows(out, ref, scale, "%s %dx%d wall=%d" % (kind, ns, nt, wall))
+    if ns == 1 and not wall:
+      assert out[0] == 0.0 and (nt < 3 or out[1] == 0.0)
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_source_target_without_sources_gives_zeros(wall):
+  from rigidmultiblobswall_amd import laplace
+  tgt = _cloud(77, 4)[0]
+  e = np.zeros((0, 3))
+  out = laplace.Laplace_single_layer_operator_source_target_hip(e, tgt, np.zeros(0), np.zeros(0), wall=wall)
+  assert out.shape == (77,) and np.all(out == 0.0)
+  out = laplace.Laplace_double_layer_operator_source_target_hip(e, tgt, np.zeros(0), np.zeros(0), e, wall=wall)
+  assert out.shape == (77,) and np.all(out == 0.0)
+
+
+def _clustered_cloud(n, seed):
+  """Clusters spread over 1e6 with nodes at 1e-6 ... 1e2 from their centre (z > 0): separations from ~1e-6 to ~1e6,
+  every pair at least 1e-7 apart."""
+  rng = np.random.RandomState(seed)
+  ncl = 24
+  centres = np.column_stack([rng.uniform(-5e5, 5e5, ncl), rng.uniform(-5e5, 5e5, ncl), rng.uniform(200.0, 1e6, ncl)])
+  which = rng.randint(ncl, size=n)
+
+  def place(k):
+    u = rng.randn(k, 3)
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    return (10.0 ** rng.uniform(-6, 2, k))[:, None] * u
+  r = centres[which] + place(n)
+  while True:
+    d2 = np.einsum("ijk,ijk->ij", r[:, None, :] - r[None, :, :], r[:, None, :] - r[None, :, :])
+    np.fill_diagonal(d2, np.inf)
+    bad = np.unique(np.nonzero(np.triu(d2 < 1e-14, 1))[1])     # the later node of each close pair
+    if not len(bad):
+      break
+    r[bad] = centres[which[bad]] + place(len(bad))
+  nrm = rng.randn(n, 3)
+  nrm /= np.linalg.norm(nrm, axis=1)[:, None]
+  return r, nrm, 0.2 + rng.rand(n), 0.5 + rng.rand(n)
+
+
+def _one_pair(kind, r, f, w, nrm, j, wall):
+  """The closed-form pair values of source j at every node (extended precision): free term (skipped at j) + image."""
+  nv = None if nrm is None else nrm[j:j + 1]
+  return lapnp.apply_ext(kind, r[j:j + 1], f[j:j + 1], w[j:j + 1], nv, wall=wall, tgt=r)
+
+
+def _cdiv(a, b):
+  return -(-a // b)
+
+
+def _chunks_for(n, forced):
+  """choose_chunks (rmb_plan.hip) for a forced count: at most ceil(n / 128) chunks, the length rounded up to a multiple
+  of 4 (the waves of a workgroup).  -> (chunks, chunk length)"""
+  c = max(1, min(forced, _cdiv(n, 128)))
+  length = 4 * _cdiv(_cdiv(n, c), 4)
+  return _cdiv(n, length), length
+
+
+def _onehot_bound(out, ref, scale, what, units=16):
+  """|d_i| <= units eps (free + image scale) per component; returns the worst ratio in units of eps."""
+  ratio = _ratios(out, ref, scale) / EPS
+  _note("one-hot |d|/(eps A)", ratio.max())
+  assert ratio.max() <= units, (what, float(ratio.max()), int(ratio.argmax()))
+  return ratio.max()
+
+
+ONEHOT_N = 1100
+ONEHOT_J = [0, 1, 3, 4, 63, 64, 511, 512, 513, ONEHOT_N - 1]
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_one_hot_sources_through_the_wrappers(wall):
+  """A single nonzero field value at j: every target holds one free term and its image, each a few eps; target j
+  holds exactly 0 without the wall.  Pins the per-pair arithmetic and each record slot one source at a time."""
+  r, nrm, w, vals = _clustered_cloud(ONEHOT_N, 21)
+  for j in ONEHOT_J:
+    f = np.zeros(ONEHOT_N)
+    f[j] = vals[j]
+    for kind in "SDGP":
+      nv = nrm if kind in "DG" else None
+      out = _wrap(kind, r, f, w, nv, wall)
+      ref, scale = _one_pair(kind, r, f, w, nv, j, wall)
+      _onehot_bound(out, ref, scale, "%s j=%d wall=%d" % (kind, j, wall))
+      if not wall:
+        assert np.all(out[j] == 0.0), (kind, j)
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_one_hot_sources_and_fused_slots_through_forced_chunks(wall):
+  """The device entries with 3 forced chunks (boundaries inside a 64-target block), one j on each side of each
+  boundary; then one-hot p at j1 and q at j2 != j1 with alpha != 0 in both fused sweeps: the -D / +S / +alpha p and
+  2G / -2P folding, and the p and q record slots not swapped."""
+  from rigidmultiblobswall_amd.context import MobilityContext
+  r, nrm, w, vals = _clustered_cloud(ONEHOT_N, 22)
+  nch, length = _chunks_for(ONEHOT_N, 3)
+  assert nch == 3 and length % 64 != 0
+  js = sorted(set(ONEHOT_J + [length - 1, length, 2 * length - 1, 2 * length]))
+  rt, nt_, wt = _dev(r, nrm, w)
+  alpha = 0.625
+  ctx = MobilityContext(0)
+  try:
+    for chunks in (3, 1):
+      ctx.set_option("chunks", chunks)
+      for j in js:
+        f = np.zeros(ONEHOT_N)
+        f[j] = vals[j]
+        ft, = _dev(f)
+        for kind, run, factor in (
+            ("D", lambda: ctx.laplace_operator_device(rt, wt, p=ft, normals=nt_, wall=wall), -1.0),
+            ("S", lambda: ctx.laplace_operator_device(rt, wt, q=ft, alpha=alpha, wall=wall), 1.0),
+            ("G", lambda: ctx.laplace_gradient_device(rt, wt, p=ft, normals=nt_, wall=wall), 2.0),
+            ("P", lambda: ctx.laplace_gradient_device(rt, wt, q=ft, wall=wall), -2.0)):
+          out = run().cpu().numpy()
+          assert ctx.last_launch()["chunks"] == _chunks_for(ONEHOT_N, chunks)[0]
+          nv = nrm if kind in "DG" else None
+          ref, scale = _one_pair(kind, r, f, w, nv, j, wall)
+          _onehot_bound(out, factor * ref, abs(factor) * scale, "%s j=%d chunks=%d wall=%d" % (kind, j, chunks, wall))
+          if not wall:
+            assert np.all(out.reshape(ONEHOT_N, -1)[j] == 0.0), (kind, j)
+      for j1, j2 in ((0, 1), (64, 63), (length - 1, length), (2 * length, 512), (ONEHOT_N - 1, 0)):
+        p, q = np.zeros(ONEHOT_N), np.zeros(ONEHOT_N)
+        p[j1], q[j2] = vals[j1], -vals[j2]
+        pt, qt = _dev(p, q)
+        refD, sD = _one_pair("D", r, p, w, nrm, j1, wall)
+        refS, sS = _one_pair("S", r, q, w, None, j2, wall)
+        ap = alpha * p.astype(lapnp.EXT)
+        out = ctx.laplace_operator_device(rt, wt, p=pt, q=qt, normals=nt_, alpha=alpha, wall=wall).cpu().numpy()
+        _onehot_bound(out, ap - refD + refS, np.abs(alpha * p) + sD + sS, "operator %d/%d wall=%d" % (j1, j2, wall))
+        refG, sG = _one_pair("G", r, p, w, nrm, j1, wall)
+        refP, sP = _one_pair("P", r, q, w, None, j2, wall)
+        out = ctx.laplace_gradient_device(rt, wt, p=pt, q=qt, normals=nt_, wall=wall).cpu().numpy()
+        _onehot_bound(out, 2 * refG - 2 * refP, 2 * (sG + sP), "gradient %d/%d wall=%d" % (j1, j2, wall))
+  finally:
+    ctx.set_option("chunks", 0)
+    ctx.close()
+
+
+def _boundary_rows(n, lengths, rng, n_random=32):
+  rows = {n - 1}
+  for b in [64, 128, 192, 512, 1024] + [k * L for L in lengths for k in (1, 2, 3)]:
+    if 0 < b < n:
+      rows.update((b - 1, b))
+  rows.update(rng.choice(n, n_random, replace=False).tolist())
+  return np.array(sorted(rows))
+
+
+_FORCED = [1, 2, 3, 7, 33, 10000]
+
+
+@pytest.mark.parametrize("n", [129, 300, 1000, 5003])
+@pytest.mark.parametrize("wall", [0, 1])
+def test_forced_source_chunks_of_the_fused_sweeps(wall, n):
+  """Both fused sweeps in their three forms at forced chunk counts: k = 1 takes the in-kernel alpha c write, k > 1 the
+  finalize kernel; at n = 300, k = 7 gives 3 chunks of 100 whose boundaries fall inside the 64-target blocks [64, 128)
+  and [192, 256).  Bitwise repeatable, within the bound, and the same across k to 1e-14."""
+  from rigidmultiblobswall_amd.context import MobilityContext
+  r, nrm, p, w, q = _cloud(n, 5000 + n)
+  rows = None if n <= 1025 else _boundary_rows(n, [_chunks_for(n, k)[1] for k in _FORCED], np.random.RandomState(n))
+  ref = {kind: lapnp.apply_ext(kind, r, p if kind in "DG" else q, w, nrm if kind in "DG" else None, wall=wall,
+                               targets_idx=rows) for kind in "SDGP"}
+  pe = (p if rows is None else p[rows]).astype(lapnp.EXT)
+  alpha = -0.375
+  # form -> (expected, scale)
+  expect = {("op", "p"): (alpha * pe - ref["D"][0], np.abs(alpha * pe).astype(np.float64) + ref["D"][1]),
+            ("op", "q"): ref["S"],
+            ("op", "pq"): (alpha * pe - ref["D"][0] + ref["S"][0],
+                           np.abs(alpha * pe).astype(np.float64) + ref["D"][1] + ref["S"][1]),
+            ("grad", "p"): (2 * ref["G"][0], 2 * ref["G"][1]),
+            ("grad", "q"): (-2 * ref["P"][0], 2 * ref["P"][1]),
+            ("grad", "pq"): (2 * ref["G"][0] - 2 * ref["P"][0], 2 * (ref["G"][1] + ref["P"][1]))}
+  rt, nt_, pt, wt, qt = _dev(r, nrm, p, w, q)
+  ctx = MobilityContext(0)
+
+  def run(form):
+    sweep, fields = form
+    kw = dict(p=pt if "p" in fields else None, q=qt if "q" in fields else None, normals=nt_, wall=wall)
+    if sweep == "op":
+      return ctx.laplace_operator_device(rt, wt, alpha=alpha, **kw)          # q only: alpha is dropped by design
+    return ctx.laplace_gradient_device(rt, wt, **kw)
+  first = {}
+  try:
+    for k in _FORCED:
+      ctx.set_option("chunks", k)
+      nch, length = _chunks_for(n, k)
+      if n == 300 and k == 7:
+        assert (nch, length) == (3, 100)
+      for form, (exp, scale) in expect.items():
+        out = run(form)
+        assert ctx.last_launch()["chunks"] == nch, (form, k)
+        assert torch.equal(out, run(form)), (form, k)                         # bit-reproducible
+        o = out.cpu().numpy().reshape(n, -1)
+        _assert_rows(o if rows is None else o[rows], exp, scale, "%s k=%d n=%d wall=%d" % (form, k, n, wall))
+        if form in first:
+          assert rel_err(o, first[form]) <= 1e-14, (form, k)
+        else:
+          first[form] = o
+  finally:
+    ctx.set_option("chunks", 0)
+    ctx.close()
+
+
+def _inner(a, b):
+  return float(torch.sum(a * b))
+
+
+@pytest.mark.parametrize("n", [65539, 200003])
+@pytest.mark.parametrize("wall", [0, 1])
+def test_large_n_adjoint_identities_and_sampled_rows(wall, n):
+  """No all-pairs reference at this size: the identities exact in real arithmetic (checked on CPU in
+  test_laplace_host.py) -- W-symmetry of S, D adjoint to -n.P, G self-adjoint -- each to 1e-12 of its Cauchy-Schwarz
+  product, at the default chunking and at 7 forced chunks; and ~100 sampled rows (tile and chunk edges, the last row,
+  32 random rows) against the float64 restatement with the per-target bound."""
+  from rigidmultiblobswall_amd.context import MobilityContext
+  r, nrm, f, w, g = _cloud(n, 7000 + (n % 97) + wall)
+  mu = np.random.RandomState(n % 89).randn(n, 3)
+  rt, nt_, ft, wt, gt, mut = _dev(r, nrm, f, w, g, mu)
+  wv, nv, muv = wt, nt_.view(-1, 3), mut.view(-1, 3)
+  ctx = MobilityContext(0)
+  rng = np.random.RandomState(n)
+  refs = None
+  try:
+    for forced in (0, 7):
+      ctx.set_option("chunks", forced)
+      S_f = ctx.laplace_operator_device(rt, wt, q=ft, wall=wall)
+      lengths = [_chunks_for(n, ctx.last_launch()["chunks"])[1]]
+      S_g = ctx.laplace_operator_device(rt, wt, q=gt, wall=wall)
+      D_f = -ctx.laplace_operator_device(rt, wt, p=ft, normals=nt_, wall=wall)
+      P_g = -0.5 * ctx.laplace_gradient_device(rt, wt, q=gt, wall=wall).view(-1, 3)
+      G_f = 0.5 * ctx.laplace_gradient_device(rt, wt, p=ft, normals=nt_, wall=wall).view(-1, 3)       # G[f; nu]
+      G_g = 0.5 * ctx.laplace_gradient_device(rt, wt, p=gt, normals=mut, wall=wall).view(-1, 3)      # G[g; mu]
+      checks = (
+          ("S", _inner(wv * gt, S_f), _inner(wv * ft, S_g),
+           max(float((wv * gt).norm() * S_f.norm()), float((wv * ft).norm() * S_g.norm()))),
+          ("D/P", _inner(wv * gt, D_f), -_inner(wv * ft, (nv * P_g).sum(1)),
+           max(float((wv * gt).norm() * D_f.norm()), float((wv * ft).norm() * (nv * P_g).sum(1).norm()))),
+          ("G", _inner(wv * gt, (muv * G_f).sum(1)), _inner(wv * ft, (nv * G_g).sum(1)),
+           max(float((wv * gt).norm() * (muv * G_f).sum(1).norm()), float((wv * ft).norm() * (nv * G_g).sum(1).norm()))))
+      for what, lhs, rhs, cs in checks:
+        _note("identity |d|/CS", abs(lhs - rhs) / cs)
+        assert abs(lhs - rhs) <= 1e-12 * cs, (what, forced, lhs, rhs, cs)
+      if refs is None:
+        rows = _boundary_rows(n, lengths + [_chunks_for(n, 7)[1]], rng)
+        refs = {k: lapnp.apply(k, r, fld, w, nn, wall=wall, targets_idx=rows, block=8, with_scale=True)
+                for k, fld, nn in (("S", f, None), ("D", f, nrm), ("G", f, nrm), ("P", g, None))}
+      for kind, out in (("S", S_f), ("D", D_f), ("G", G_f), ("P", P_g)):
+        o = out.cpu().numpy().reshape(n, -1)[rows]
+        ratio = _ratios(o, refs[kind][0], refs[kind][1])
+        _note("per-target |d|/A, sampled rows at large N", ratio.max())
+        assert np.all(np.isfinite(o)) and ratio.max() <= TOL, (kind, forced, float(ratio.max()), int(rows[ratio.argmax()]))
+  finally:
+    ctx.set_option("chunks", 0)
+    ctx.close()
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_nodes_near_the_wall_coincident_nodes_and_zero_fields(wall):
+  """Nodes at z = 1e-4 and 1e-2 (the self-image dominates); two distinct nodes at one point (non-finite exactly at those
+  two targets, as the Stokes NaN policy); zero field and zero weights give exact zeros."""
+  n = 300
+  r, nrm, f, w, _ = _cloud(n, 31 + wall)
+  r[5, 2], r[70, 2], r[200, 2] = 1e-4, 1e-2, 1e-4
+  for kind in "SDGP":
+    nv = nrm if kind in "DG" else None
+    out = _wrap(kind, r, f, w, nv, wall)
+    ref, scale = lapnp.apply_ext(kind, r, f, w, nv, wall=wall)
+    _assert_rows(out, ref, scale, "near wall %s wall=%d" % (kind, wall))
+    assert np.all(_wrap(kind, r, np.zeros(n), w, nv, wall) == 0.0)
+    assert np.all(_wrap(kind, r, f, np.zeros(n), nv, wall) == 0.0)
+  rc = r.copy()
+  rc[80] = rc[37]
+  for kind in "SDGP":
+    nv = nrm if kind in "DG" else None
+    out = _wrap(kind, rc, f, w, nv, wall).reshape(n, -1)
+    bad = ~np.all(np.isfinite(out), axis=1)
+    assert np.array_equal(np.nonzero(bad)[0], [37, 80]), (kind, np.nonzero(bad)[0][:8])
+    assert not np.any(np.isfinite(out[[37, 80]])), kind   # non-finite (rsqrt(0) is NaN here, inf in the reference)
+    keep = np.setdiff1d(np.arange(n), [37, 80])
+    ref, scale = lapnp.apply_ext(kind, rc, f, w, nv, wall=wall, targets_idx=keep)
+    _assert_rows(out[keep], ref, scale, "coincident %s wall=%d" % (kind, wall))
+
+
+def test_node_on_the_wall_is_non_finite_only_at_itself():
+  n = 200
+  r, nrm, f, w, _ = _cloud(n, 41)
+  r[17, 2] = 0.0
+  keep = np.setdiff1d(np.arange(n), [17])
+  for kind in "SDGP":
+    nv = nrm if kind in "DG" else None
+    out = _wrap(kind, r, f, w, nv, 1).reshape(n, -1)
+    assert not np.any(np.isfinite(out[17])), kind
+    ref, scale = lapnp.apply_ext(kind, r, f, w, nv, wall=1, targets_idx=keep)
+    _assert_rows(out[keep], ref, scale, "z=0 %s" % kind)
+    assert np.all(np.isfinite(_wrap(kind, r, f, w, nv, 0))), kind      # no image, nothing coincides
+
+
+def test_empty_inputs_give_empty_outputs():
+  from rigidmultiblobswall_amd import laplace
+  from rigidmultiblobswall_amd.context import MobilityContext
+  e3, e = np.zeros((0, 3)), np.zeros(0)
+  for wall in (0, 1):
+    for kind in "SDGP":
+      out = _wrap(kind, e3, e, e, e3 if kind in "DG" else None, wall)
+      assert out.size == 0, kind
+    assert laplace.Laplace_single_layer_operator_source_target_hip(e3, e3, e, e, wall=wall).shape == (0,)
+    assert laplace.Laplace_double_layer_operator_source_target_hip(e3, e3, e, e, e3, wall=wall).shape == (0,)
+    assert laplace.Laplace_single_layer_operator_source_target_hip(_cloud(5, 1)[0], e3, np.ones(5), np.ones(5),
+                                                                    wall=wall).shape == (0,)
+  ctx = MobilityContext(0)
+  r, p = _dev(e3, e)
+  assert ctx.laplace_operator_device(r, p, p=p, q=p, normals=r, alpha=0.5).numel() == 0
+  assert ctx.laplace_gradient_device(r, p, p=p, q=p, normals=r, wall=True).numel() == 0
+  ctx.close()
+
+
+def test_wrapper_input_layouts_and_sizes():
+  """float32, (N, 3) against flat, strided and Fortran-ordered inputs give bitwise the contiguous float64 call; inputs
+  are not mutated; field, weight and normal arrays of the wrong size raise ValueError."""
+  from rigidmultiblobswall_amd import laplace
+  n = 130
+  r, nrm, f, w, _ = _cloud(n, 51)
+  for kind in "SDGP":
+    nv = nrm if kind in "DG" else None
+    base = _wrap(kind, r, f, w, nv, 1)
+    args = [r, f, w] + ([nv] if nv is not None else [])
+    copies = [a.copy() for a in args]
+    r32, f32, w32 = r.astype(np.float32), f.astype(np.float32), w.astype(np.float32)
+    n32 = None if nv is None else nv.astype(np.float32)
+    assert np.array_equal(_wrap(kind, r32, f32, w32, n32, 1),
+                          _wrap(kind, r32.astype(np.float64), f32.astype(np.float64), w32.astype(np.float64),
+                                None if n32 is None else n32.astype(np.float64), 1)), kind
+    assert np.array_equal(_wrap(kind, r.reshape(-1), f, w, None if nv is None else nv.reshape(-1), 1), base), kind
+    rs = np.zeros((n, 6))
+    rs[:, ::2] = r                                          # strided view
+    fs = np.zeros(2 * n)
+    fs[::2] = f
+    assert np.array_equal(_wrap(kind, rs[:, ::2], fs[::2], np.asfortranarray(w), None if nv is None else
+                                np.asfortranarray(nv), 1), base), kind
+    assert np.array_equal(_wrap(kind, np.asfortranarray(r), f, w, nv, 1), base), kind
+    for a, c in zip(args, copies):
+      assert np.array_equal(a, c), kind                     # inputs untouched
+    with pytest.raises(ValueError):
+      _wrap(kind, r, f[:-1], w, nv, 1)
+    with pytest.raises(ValueError):
+      _wrap(kind, r, f, np.append(w, 1.0), nv, 1)
+    if nv is not None:
+      with pytest.raises(ValueError):
+        _wrap(kind, r, f, w, nv[:-1], 1)
+  src, tgt = r[:40], r[40:] + 0.1
+  with pytest.raises(ValueError):
+    laplace.Laplace_single_layer_operator_source_target_hip(src, tgt, f[:41], w[:40])
+  with pytest.raises(ValueError):
+    laplace.Laplace_double_layer_operator_source_target_hip(src, tgt, f[:40], w[:40], nrm[:39])
+
+
+def test_device_entries_refuse_a_wrong_out_and_write_a_right_one_in_place():
+  """A caller's out= reaches the kernel unchecked unless the context checks it.  Every wrong out here has storage for
+  the whole write, so a tree without the check cannot write out of bounds: the test sees the sentinel change."""
+  from rigidmultiblobswall_amd.context import MobilityContext
+  n = 257
+  r, nrm, p, w, q = _dev(*_cloud(n, 61))
+  ctx = MobilityContext(0)
+  sentinel = -12345.0
+  for size, call in ((n, lambda out: ctx.laplace_operator_device(r, w, p=p, q=q, normals=nrm, alpha=0.5, out=out)),
+                     (3 * n, lambda out: ctx.laplace_gradient_device(r, w, p=p, q=q, normals=nrm, wall=True, out=out))):
+    big = torch.full((size + 64,), sentinel, dtype=torch.float64, device="cuda:0")
+    strided = torch.full((2 * size,), sentinel, dtype=torch.float64, device="cuda:0")
+    as_int = torch.full((size,), 7, dtype=torch.int64, device="cuda:0")
+    f32 = torch.full((2 * size,), sentinel, dtype=torch.float32, device="cuda:0")
+    for wrong in (big[:size - 1], strided[::2], as_int, f32[:size]):
+      with pytest.raises(ValueError):
+        call(wrong)
+    torch.cuda.synchronize()
+    assert torch.all(big == sentinel) and torch.all(strided == sentinel) and torch.all(as_int == 7)
+    assert torch.all(f32 == sentinel)
+    out = big[:size]
+    res = call(out)
+    assert res.data_ptr() == out.data_ptr()
+    assert torch.equal(out, call(None)) and torch.all(big[size:] == sentinel)
+  ctx.close()
+
+
+def _slip_deck(wall, seed):
+  """3 Janus shells and 2 sprinklers (blob order), random orientations and heights, well apart; every term of the
+  slip nonzero: k, e (redrawn), c0, b, H, Dc != 1; normals, mu and weights from the fixtures."""
+  gj = load_golden(os.path.join(GOLDEN, "g12_laplace_slip_janus_wall.npz"))
+  gs = load_golden(os.path.join(GOLDEN, "g12_laplace_slip_sprinklers_wall.npz"))
+  rng = np.random.RandomState(seed)
+  refs = [gj["vertex"]] * 3 + [gs["vertex"]] * 2
+  lap = [gj["laplace"].copy() for _ in range(3)] + [gs["laplace"].copy() for _ in range(2)]
+  for L in lap:
+    L[:, 3] = 0.2 + rng.rand(len(L))
+    L[:, 4] = 0.5 + rng.rand(len(L))
+  loc = np.array([[-24.0, 0.0, 1.5], [-20.0, 3.0, 1.5], [-16.0, -3.0, 1.5], [-2.0, 0.0, 7.0], [14.0, 0.0, 7.0]])
+  loc[:, 2] += rng.rand(5)
+  quat = rng.randn(5, 4)
+  quat /= np.linalg.norm(quat, axis=1)[:, None]
+  return refs, np.vstack(lap), loc, quat, np.array([1.0, 0.2, -0.1, 0.05, 0.02, 0.01, -0.03, 0.015, 0.01]), 0.7
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_phoretic_slip_matches_the_dense_solve(wall):
+  """PhoreticSlip at GMRES tolerance 1e-12 against np.linalg.solve of the dense concentration problem
+  (_laplace_numpy.dense_slip) on a 270-node deck with every term of the slip nonzero."""
+  from rigidmultiblobswall_amd.laplace import PhoreticSlip
+  from rigidmultiblobswall_amd.rigid import RigidSuspension
+  refs, lap, loc, quat, bg, Dc = _slip_deck(wall, 71 + wall)
+  r, n = lapnp.bodies_to_lab(refs, [lap[:42, 0:3]] * 3 + [lap[126:198, 0:3]] * 2, loc, quat)
+  assert len(r) == 270
+  d2 = np.einsum("ijk,ijk->ij", r[:, None] - r[None], r[:, None] - r[None]) + np.diag(np.full(270, np.inf))
+  assert d2.min() > 1e-4 and r[:, 2].min() > 0.3
+  c_ref, slip_ref = lapnp.dense_slip(r, n, lap[:, 6], lap[:, 3], lap[:, 4], lap[:, 5], bg, Dc, wall=wall)
+  susp = RigidSuspension(refs, loc, quat, 0.25, 1.0, wall=bool(wall), device="cuda:0")
+  assert np.abs(susp.r_dev.view(-1, 3).cpu().numpy() - r).max() <= 1e-13 * np.abs(r).max()
+  ps = PhoreticSlip(susp, lap, background=bg, diffusion_coefficient=Dc, tolerance=1e-12, wall=bool(wall))
+  slip = ps.compute(susp).cpu().numpy()
+  err_c = rel_err(ps.concentration.cpu().numpy(), c_ref)
+  err_s = rel_err(slip, slip_ref)
+  _note("dense slip rel (c, slip)", max(err_c, err_s))
+  assert err_c <= 1e-9 and err_s <= 1e-9, (err_c, err_s)
+  assert np.linalg.norm(np.einsum("ik,ik->i", n, slip)) <= 1e-12 * np.linalg.norm(slip)
+  susp.close()

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_golden
+from conftest import GOLDEN, golden_files, load_golden
 import _laplace_numpy as lapnp
 
 DECK = """scheme                                   {scheme}
@@ -130,3 +130,83 @@ def test_numpy_restatement_matches_reference_operators(name, kind, normals, st, 
   ref = g["%s_wall%d" % (name, wall)]
   assert np.all(np.isfinite(out))
   assert np.linalg.norm(out.reshape(-1) - ref) <= 1e-13 * np.linalg.norm(ref)
+
+
+# --- the extended-precision reference and the dense matrices the GPU tests rest on (tests/_laplace_numpy.py) ----------
+@pytest.mark.parametrize("wall", [0, 1])
+@pytest.mark.parametrize("name,kind,normals,st", _OPS, ids=["%s-%s" % (o[0], lapnp.EXT_NAME) for o in _OPS])
+def test_extended_restatement_matches_reference_operators(name, kind, normals, st, wall):
+  g = load_golden(os.path.join(GOLDEN, "g12_laplace_operators.npz"))
+  out, scale = lapnp.apply_ext(kind, g["r"], g["field"], g["weights"], g["normals"] if normals else None, wall=wall,
+                               tgt=g["target"] if st else None)
+  ref = g["%s_wall%d" % (name, wall)]
+  out = out.astype(np.float64).reshape(-1)
+  assert np.all(np.isfinite(out)) and np.all(scale > 0)
+  assert np.linalg.norm(out - ref) <= 1e-13 * np.linalg.norm(ref)
+  # the scale bounds every value: |value_i| <= A_i (per component for G, P)
+  assert np.all(np.abs(out.reshape(len(scale), -1)) <= scale[:, None] * (1 + 1e-12))
+
+
+def _slip_inputs(g):
+  nb = len(g["locations"])
+  L = np.tile(g["laplace"], (nb, 1))
+  r, n = lapnp.bodies_to_lab([g["vertex"]] * nb, [g["laplace"][:, 0:3]] * nb, g["locations"], g["quaternions"])
+  return r, n, L
+
+
+SLIP = [os.path.basename(p) for p in golden_files("g12_laplace_slip_*.npz")]
+
+
+@pytest.mark.parametrize("fname", SLIP, ids=[f[17:-4] for f in SLIP])
+def test_dense_slip_matches_reference_calc_slip(fname):
+  """The reference's calc_slip ran GMRES to 1e-10; the dense solve is exact up to conditioning.  Observed: 4.3e-11 ...
+  2.9e-10 on the concentration, 6.3e-11 ... 6.8e-10 on the slip (janus_wall the largest)."""
+  g = load_golden(os.path.join(GOLDEN, fname))
+  r, n, L = _slip_inputs(g)
+  c, slip = lapnp.dense_slip(r, n, L[:, 6], L[:, 3], L[:, 4], L[:, 5], g["background"], float(g["diffusion_coefficient"]),
+                             wall=str(g["domain"]) == "single_wall")
+  err_c = np.linalg.norm(c - g["concentration"]) / np.linalg.norm(g["concentration"])
+  err_s = np.linalg.norm(slip.reshape(-1) - g["slip"].reshape(-1)) / np.linalg.norm(g["slip"])
+  assert err_c <= 1e-9 and err_s <= 1e-9, (err_c, err_s)
+
+
+def _identity_cloud(n, seed):
+  rng = np.random.RandomState(seed)
+  r = np.column_stack([4 * rng.rand(n), 4 * rng.rand(n), 0.3 + 2 * rng.rand(n)])
+  nrm = rng.randn(n, 3)
+  nrm /= np.linalg.norm(nrm, axis=1)[:, None]
+  return r, nrm, 0.2 + rng.rand(n), rng.randn(n), rng.randn(n)
+
+
+@pytest.mark.parametrize("wall", [0, 1])
+def test_dense_matrices_satisfy_the_adjoint_identities(wall):
+  """The identities the large-N GPU tests use, exact in real arithmetic with and without the image (the kept self-image
+  included): W-symmetry of S, D = -(n . P)^T under the weights, and G self-adjoint under the weights."""
+  n = 300
+  r, nrm, w, f, g = _identity_cloud(n, 40 + wall)
+  S, D = lapnp.dense("S", r, w, wall=wall), lapnp.dense("D", r, w, nrm, wall=wall)
+  G, P = lapnp.dense("G", r, w, nrm, wall=wall), lapnp.dense("P", r, w, wall=wall)
+  # each matrix is the operator it restates
+  for kind, M, nv in (("S", S, None), ("D", D, nrm), ("G", G, nrm), ("P", P, None)):
+    ref = lapnp.apply(kind, r, f, w, nv, wall=wall)
+    assert np.linalg.norm((M @ f).reshape(-1) - ref.reshape(-1)) <= 1e-14 * np.linalg.norm(ref), kind
+  W = np.diag(w)
+  tol = 1e-13
+
+  def close(a, b):
+    return np.abs(a - b).max() <= tol * np.abs(a).max()
+  assert close(W @ S, (W @ S).T)                                          # <w g, S f> = <w f, S g>
+  nP = np.einsum("ik,ikj->ij", nrm, P)                                    # (n . P[g])_i
+  assert close(W @ D, -(W @ nP).T)                                        # <w g, D[p]> = -<w p, n . P[g]>
+  mu = np.random.RandomState(7).randn(n, 3)
+  Gnu = lapnp.dense("G", r, w, nrm, wall=wall)                            # G[f; nu]
+  Gmu = lapnp.dense("G", r, w, mu, wall=wall)                             # G[a; mu]
+  lhs = W @ np.einsum("ik,ikj->ij", mu, Gnu)                              # sum w a (mu . G[f; nu])
+  rhs = W @ np.einsum("ik,ikj->ij", nrm, Gmu)                             # sum w f (nu . G[a; mu])
+  assert close(lhs, rhs.T)
+  # and on vectors, the form the GPU tests use
+  a = f
+  assert abs(np.sum(w * g * (S @ f)) - np.sum(w * f * (S @ g))) <= tol * np.linalg.norm(w * g) * np.linalg.norm(S @ f)
+  assert abs(np.sum(w * a * np.einsum("ik,ik->i", mu, np.einsum("ikj,j->ik", Gnu, g))) -
+             np.sum(w * g * np.einsum("ik,ik->i", nrm, np.einsum("ikj,j->ik", Gmu, a)))) <= \
+      tol * np.linalg.norm(w * a) * np.linalg.norm(np.einsum("ikj,j->ik", Gnu, g))
