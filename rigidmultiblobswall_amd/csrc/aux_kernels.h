@@ -9,12 +9,10 @@
 // the routine returns for one source and what superposition gives; only periodic_length = 0 (the reference's periodic
 // branch divides by the unwrapped distance).
 //
-// HOW: same one-sided skeleton as st_kernels.h -- lane = target, an LDS tile of source records shared by the four waves
-// of a workgroup (each wave takes every fourth source), source chunks over blockIdx.y with a fixed-order reduction, no
-// atomics: bit-reproducible.  The nine-term contraction of the reference is (r.n)(r.v) r; divisions become one
-// inverse square root per distance.  HBM traffic is the records once per target tile; the kernel is fp64-VALU bound
-// like every pair sweep here (VALU instructions per source-target pair in this build: pressure 21 / 42 with the wall,
-// double layer 35 / 82 with the wall images / 50 for the RPY form).
+// HOW: policies of the one-sided frame (onesided_kernels.h).  The nine-term contraction of the reference is
+// (r.n)(r.v) r; divisions become one inverse square root per distance.  HBM traffic is the records once per target tile;
+// the kernel is fp64-VALU bound like every pair sweep here (VALU instructions per source-target pair in this build:
+// pressure 19 / 40 with the wall, double layer 33 / 80 with the wall images / 48 for the RPY form).
 #pragma once
 #include "matvec_kernels.h"
 
@@ -22,16 +20,12 @@ namespace rmb {
 
 enum { AUX_P_FREE = 0, AUX_P_WALL = 1, AUX_DL_FREE = 2, AUX_DL_WALL = 3, AUX_DL_RPY = 4 };
 
-struct AuxArgs {
+struct AuxArgs : OneSidedArgs {   // out: pressure [nt];  double layer [3 nt]
   const double* src;    // [3 ns]
   const double* tgt;    // [3 nt]
   const double* v0;     // pressure: force [3 ns];  double layer: normals [3 ns]
   const double* v1;     // double layer: vector [3 ns]
   const double* w;      // double layer: weights [ns]
-  double* out;          // pressure [nt];  double layer [3 nt]
-  double* partial;      // [n_chunks][NOUT][n_tgt_pad]
-  long ns, nt, n_tgt_pad, chunk_len;
-  int n_chunks;
   double prefactor;     // 1/(4 pi)  |  -3/(4 pi)
   double a2;            // RPY double layer: blob radius squared
 };
@@ -108,85 +102,48 @@ __device__ __forceinline__ void aux_pair(const AuxArgs& a, double dx, double dy,
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void aux_sweep_kernel(const AuxArgs a) {
-  constexpr int NOUT = AuxShape<MODE>::NOUT, R2 = AuxShape<MODE>::REC2;
-  __shared__ double2 tile[kTile * R2];
-  __shared__ double red[(kWaves - 1) * NOUT * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const long ti = 64L * blockIdx.x + lane;
-  const bool valid = ti < a.nt;
-  const long tc = valid ? ti : a.nt - 1;
-  const double xt = a.tgt[3 * tc], yt = a.tgt[3 * tc + 1], zt = a.tgt[3 * tc + 2];
-  const long c0 = (long)blockIdx.y * a.chunk_len;
-  long c1 = c0 + a.chunk_len;
-  if (c1 > a.ns) c1 = a.ns;
-  double acc[NOUT];
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) acc[c] = 0.0;
-  for (long j0 = c0; j0 < c1; j0 += kTile) {
-    const int n = (int)((c1 - j0 < kTile) ? (c1 - j0) : kTile);
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kBlock) {
-      const long j = j0 + t;
-      double2* rec = tile + t * R2;
-      rec[0] = make_double2(a.src[3 * j], a.src[3 * j + 1]);
-      rec[1] = make_double2(a.src[3 * j + 2], a.v0[3 * j]);
-      rec[2] = make_double2(a.v0[3 * j + 1], a.v0[3 * j + 2]);
-      if constexpr (R2 == 5) {
-        rec[3] = make_double2(a.v1[3 * j], a.v1[3 * j + 1]);
-        rec[4] = make_double2(a.v1[3 * j + 2], a.w[j]);
-      }
+template <int MODE> struct AuxOp {
+  typedef AuxArgs Args;
+  struct Target { double x, y, z; };
+  static constexpr int NOUT = AuxShape<MODE>::NOUT, REC2 = AuxShape<MODE>::REC2;
+  static constexpr bool SHARDED = false, SKIP_OWN_TILE = false;
+
+  static __device__ __forceinline__ Target load_target(const Args& a, long t) { return {a.tgt[3 * t], a.tgt[3 * t + 1], a.tgt[3 * t + 2]}; }
+
+  static __device__ __forceinline__ void stage(const Args& a, long j, double2* rec) {
+    rec[0] = make_double2(a.src[3 * j], a.src[3 * j + 1]);
+    rec[1] = make_double2(a.src[3 * j + 2], a.v0[3 * j]);
+    rec[2] = make_double2(a.v0[3 * j + 1], a.v0[3 * j + 2]);
+    if constexpr (REC2 == 5) {
+      rec[3] = make_double2(a.v1[3 * j], a.v1[3 * j + 1]);
+      rec[4] = make_double2(a.v1[3 * j + 2], a.w[j]);
     }
-    __syncthreads();
+  }
+
+  template <bool>
+  static __device__ __forceinline__ void tile_pairs(const Args& a, const double2* tile, int n, int wave, long, long,
+                                                    const Target& tg, double* acc) {
     for (int s = wave; s < n; s += kWaves) {
-      const double2* rec = tile + s * R2;
+      const double2* rec = tile + s * REC2;
       double q[7];
       const double2 p0 = rec[0], p1 = rec[1], p2 = rec[2];
       q[0] = p1.y; q[1] = p2.x; q[2] = p2.y;
-      if constexpr (R2 == 5) { const double2 p3 = rec[3], p4 = rec[4]; q[3] = p3.x; q[4] = p3.y; q[5] = p4.x; q[6] = p4.y; }
-      aux_pair<MODE>(a, xt - p0.x, yt - p0.y, zt - p1.x, zt, p1.x, q, acc);
+      if constexpr (REC2 == 5) { const double2 p3 = rec[3], p4 = rec[4]; q[3] = p3.x; q[4] = p3.y; q[5] = p4.x; q[6] = p4.y; }
+      aux_pair<MODE>(a, tg.x - p0.x, tg.y - p0.y, tg.z - p1.x, tg.z, p1.x, q, acc);
     }
   }
-  if (wave > 0) {
-    double* r = red + (wave - 1) * NOUT * 64;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) r[c * 64 + lane] = acc[c];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 0; w < kWaves - 1; ++w) {
-    const double* r = red + w * NOUT * 64;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) acc[c] += r[c * 64 + lane];
-  }
-  if (a.n_chunks == 1) {
-    if (!valid) return;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) a.out[NOUT * ti + c] = acc[c] * a.prefactor;
-  } else {
-    double* p = a.partial + (long)blockIdx.y * NOUT * a.n_tgt_pad;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) p[c * a.n_tgt_pad + ti] = acc[c];
-  }
-}
 
-template <int NOUT>
-__global__ __launch_bounds__(256) void aux_finalize_kernel(const AuxArgs a) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nt) return;
-  double s[NOUT];
+  static __device__ __forceinline__ void store(const Args& a, long t, const Target&, const double* acc) {
 #pragma unroll
-  for (int c = 0; c < NOUT; ++c) s[c] = 0.0;
-  for (int k = 0; k < a.n_chunks; ++k) {
-    const double* p = a.partial + (long)k * NOUT * a.n_tgt_pad;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) s[c] += p[c * a.n_tgt_pad + t];
+    for (int c = 0; c < NOUT; ++c) a.out[NOUT * t + c] = acc[c] * a.prefactor;
   }
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) a.out[NOUT * t + c] = s[c] * a.prefactor;
-}
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void aux_sweep_kernel(const AuxArgs a) { one_sided_sweep<AuxOp<MODE>>(a); }
+
+// the epilogue depends on the mode through NOUT alone
+template <int NOUT>
+__global__ __launch_bounds__(256) void aux_finalize_kernel(const AuxArgs a) { one_sided_finalize<AuxOp<NOUT == 1 ? AUX_P_FREE : AUX_DL_FREE>>(a); }
 
 }  // namespace rmb

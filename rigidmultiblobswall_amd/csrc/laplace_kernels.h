@@ -14,28 +14,25 @@
 //   gradient   out_t = 2 G[p]_t - 2 P[q]_t
 // The reference-shaped single operators are the same template with one term compiled out (no pass over a zero field).
 //
-// HOW: the one-sided skeleton of aux_kernels.h -- lane = target, an LDS tile of source records shared by the four waves
-// of a workgroup, source chunks over blockIdx.y with a fixed-order reduction, no atomics: bit-reproducible.  A record
-// holds the position, the normal and the two weighted fields w p, w q with their signs / factors folded in at staging,
-// so the pair loop is a handful of FMAs around one inverse square root per distance (two with the wall).  The index
-// test of the self operators runs only in the source tile that overlaps the workgroup's own 64 targets.
+// HOW: policies of the one-sided frame (onesided_kernels.h).  A record holds the position, the normal and the two weighted
+// fields w p, w q with their signs / factors folded in at staging, so the pair loop is a handful of FMAs around one inverse
+// square root per distance (two with the wall).  The index test of the self operators runs only in the source tile that
+// overlaps the workgroup's own 64 targets.
 //
-// VALU instructions per source-target pair of the pair loop in this build (tools/isa_stats.py kernel_loop_stats on
-// rmb_laplace.hip; free / with the wall images; of them fp64: one fewer to five fewer):
-//   self:            S 17 / 26   D 22 / 35   operator 22 / 35   G 30 / 51   P 21 / 35   gradient 31 / 53
-//   source -> target: S 20 / 29   D 25 / 38   (the distance test is in every pair)
+// VALU instructions per source-target pair of the pair loop in this build (tools/kernel_resources.py; free / with the
+// wall images; of them fp64: one to three fewer):
+//   self:            S 15 / 24   D 20 / 33   operator 20 / 33   G 28 / 49   P 19 / 33   gradient 29 / 51
+//   source -> target: S 18 / 27   D 23 / 36   (the distance test is in every pair)
 // The fused sweeps cost what their more expensive half costs: the operator one pass of D, the gradient one pass of G
 // plus one FMA.
 #pragma once
-#include "pair_ops.h"
+#include "onesided_kernels.h"
 
 namespace rmb {
 
-constexpr int kLapTile = 512;   // source records per LDS tile (as kTile of the other one-sided sweeps)
-
 enum { LAP_S = 0, LAP_D = 1, LAP_OPERATOR = 2, LAP_GRAD_D = 3, LAP_DIPOLE = 4, LAP_GRADIENT = 5 };
 
-struct LapArgs {
+struct LapArgs : OneSidedArgs {   // out: [nt] (S, D, operator) or [3 nt] (G, P, gradient)
   const double* src;    // [3 ns]
   const double* tgt;    // [3 nt]  (== src for the self operators)
   const double* nrm;    // normals at the sources [3 ns]   (D, G)
@@ -43,10 +40,6 @@ struct LapArgs {
   const double* p;      // field of the D / G term [ns]
   const double* q;      // field of the S / P term [ns]
   const double* c;      // operator: alpha c_t [nt], or nullptr
-  double* out;          // [nt] (S, D, operator) or [3 nt] (G, P, gradient)
-  double* partial;      // [n_chunks][NOUT][n_tgt_pad]
-  long ns, nt, n_tgt_pad, chunk_len;
-  int n_chunks;
   double sp, sq;        // folded into the records: w p sp, w q sq
   double alpha;
   double prefactor;     // 1/(4 pi)
@@ -137,99 +130,53 @@ __device__ __forceinline__ void lap_tile(const double2* tile, int n, int wave, d
   }
 }
 
-template <int OP, bool WALL, bool SELF>
-__global__ __launch_bounds__(kBlock) void laplace_sweep_kernel(const LapArgs a) {
+template <int OP, bool WALL, bool SELF> struct LapOp {
+  typedef LapArgs Args;
   using Sh = LapShape<OP>;
-  constexpr int NOUT = Sh::NOUT, R2 = Sh::REC2;
-  __shared__ double2 tile[kLapTile * R2];
-  __shared__ double red[(kWaves - 1) * NOUT * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const long tb = 64L * blockIdx.x;
-  const long ti = tb + lane;
-  const bool valid = ti < a.nt;
-  const long tc = valid ? ti : a.nt - 1;
-  const double xt = a.tgt[3 * tc], yt = a.tgt[3 * tc + 1], zt = a.tgt[3 * tc + 2];
-  const long c0 = (long)blockIdx.y * a.chunk_len;
-  long c1 = c0 + a.chunk_len;
-  if (c1 > a.ns) c1 = a.ns;
-  double acc[NOUT];
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) acc[c] = 0.0;
-  for (long j0 = c0; j0 < c1; j0 += kLapTile) {
-    const int n = (int)((c1 - j0 < kLapTile) ? (c1 - j0) : kLapTile);
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kBlock) {
-      const long j = j0 + t;
-      const double w = a.w[j];
-      double2* rec = tile + t * R2;
-      rec[0] = make_double2(a.src[3 * j], a.src[3 * j + 1]);
-      if constexpr (R2 == 4) {
-        rec[1] = make_double2(a.src[3 * j + 2], a.nrm[3 * j]);
-        rec[2] = make_double2(a.nrm[3 * j + 1], a.nrm[3 * j + 2]);
-        rec[3] = make_double2(a.sp * (w * a.p[j]), (Sh::S || Sh::P) ? a.sq * (w * a.q[j]) : 0.0);
-      } else {
-        rec[1] = make_double2(a.src[3 * j + 2], a.sq * (w * a.q[j]));
-      }
-    }
-    __syncthreads();
-    if constexpr (SELF) {
-      if (j0 < tb + 64 && tb < j0 + n) {          // wave-uniform: this tile holds some of the workgroup's own targets
-        const int so = (tc >= j0 && tc < j0 + n) ? (int)(tc - j0) : -1;
-        lap_tile<OP, WALL, 1>(tile, n, wave, xt, yt, zt, so, acc);
-      } else {
-        lap_tile<OP, WALL, 0>(tile, n, wave, xt, yt, zt, -1, acc);
-      }
-    } else {
-      lap_tile<OP, WALL, 2>(tile, n, wave, xt, yt, zt, -1, acc);
-    }
-  }
-  if (wave > 0) {
-    double* r = red + (wave - 1) * NOUT * 64;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) r[c * 64 + lane] = acc[c];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 0; w < kWaves - 1; ++w) {
-    const double* r = red + w * NOUT * 64;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) acc[c] += r[c * 64 + lane];
-  }
-  if (a.n_chunks == 1) {
-    if (!valid) return;
-    if constexpr (NOUT == 1) {
-      a.out[ti] = a.c ? __builtin_fma(a.alpha, a.c[ti], acc[0] * a.prefactor) : acc[0] * a.prefactor;
-    } else {
-#pragma unroll
-      for (int c = 0; c < NOUT; ++c) a.out[NOUT * ti + c] = acc[c] * a.prefactor;
-    }
-  } else {
-    double* p = a.partial + (long)blockIdx.y * NOUT * a.n_tgt_pad;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) p[c * a.n_tgt_pad + ti] = acc[c];
-  }
-}
+  struct Target { double x, y, z; };
+  static constexpr int NOUT = Sh::NOUT, REC2 = Sh::REC2;
+  static constexpr bool SHARDED = false, SKIP_OWN_TILE = SELF;   // source -> target: by distance, in every pair
 
+  static __device__ __forceinline__ Target load_target(const Args& a, long t) { return {a.tgt[3 * t], a.tgt[3 * t + 1], a.tgt[3 * t + 2]}; }
+
+  static __device__ __forceinline__ void stage(const Args& a, long j, double2* rec) {
+    const double w = a.w[j];
+    rec[0] = make_double2(a.src[3 * j], a.src[3 * j + 1]);
+    if constexpr (REC2 == 4) {
+      rec[1] = make_double2(a.src[3 * j + 2], a.nrm[3 * j]);
+      rec[2] = make_double2(a.nrm[3 * j + 1], a.nrm[3 * j + 2]);
+      rec[3] = make_double2(a.sp * (w * a.p[j]), (Sh::S || Sh::P) ? a.sq * (w * a.q[j]) : 0.0);
+    } else {
+      rec[1] = make_double2(a.src[3 * j + 2], a.sq * (w * a.q[j]));
+    }
+  }
+
+  template <bool OWN>
+  static __device__ __forceinline__ void tile_pairs(const Args&, const double2* tile, int n, int wave, long j0, long ti,
+                                                    const Target& tg, double* acc) {
+    if constexpr (OWN) {
+      const int so = (ti >= j0 && ti < j0 + n) ? (int)(ti - j0) : -1;   // the tile slot of the lane's own target
+      lap_tile<OP, WALL, 1>(tile, n, wave, tg.x, tg.y, tg.z, so, acc);
+    } else {
+      lap_tile<OP, WALL, SELF ? 0 : 2>(tile, n, wave, tg.x, tg.y, tg.z, -1, acc);
+    }
+  }
+
+  static __device__ __forceinline__ void store(const Args& a, long t, const Target&, const double* acc) {
+    if constexpr (NOUT == 1) {
+      a.out[t] = a.c ? __builtin_fma(a.alpha, a.c[t], acc[0] * a.prefactor) : acc[0] * a.prefactor;
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOUT; ++c) a.out[NOUT * t + c] = acc[c] * a.prefactor;
+    }
+  }
+};
+
+template <int OP, bool WALL, bool SELF>
+__global__ __launch_bounds__(kBlock) void laplace_sweep_kernel(const LapArgs a) { one_sided_sweep<LapOp<OP, WALL, SELF>>(a); }
+
+// the epilogue depends on the operator through NOUT alone
 template <int NOUT>
-__global__ __launch_bounds__(256) void laplace_finalize_kernel(const LapArgs a) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nt) return;
-  double s[NOUT];
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) s[c] = 0.0;
-  for (int k = 0; k < a.n_chunks; ++k) {
-    const double* p = a.partial + (long)k * NOUT * a.n_tgt_pad;
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) s[c] += p[c * a.n_tgt_pad + t];
-  }
-  if constexpr (NOUT == 1) {
-    a.out[t] = a.c ? __builtin_fma(a.alpha, a.c[t], s[0] * a.prefactor) : s[0] * a.prefactor;
-  } else {
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) a.out[NOUT * t + c] = s[c] * a.prefactor;
-  }
-}
+__global__ __launch_bounds__(256) void laplace_finalize_kernel(const LapArgs a) { one_sided_finalize<LapOp<NOUT == 1 ? LAP_S : LAP_DIPOLE, false, false>>(a); }
 
 }  // namespace rmb

@@ -28,7 +28,7 @@ namespace rmb {
 
 // Launch geometry shared by the kernels and the host-side plans (rmb_plan.hip): a workgroup of every pair kernel is
 // 4 waves = 256 threads, one wave per SIMD.
-constexpr int kWaves = 4;            // one-sided sweeps (matvec_kernels.h, st_kernels.h, aux_kernels.h)
+constexpr int kWaves = 4;            // one-sided sweeps (onesided_kernels.h)
 constexpr int kBlock = 64 * kWaves;
 constexpr int kSymWaves = 4;         // symmetric kernels (sym*_kernels.h)
 constexpr int kSymWavesPerEu = 4;    // register budget of sym_kernel / sym2_kernel: 4 waves per SIMD (the launch plan relies on it)

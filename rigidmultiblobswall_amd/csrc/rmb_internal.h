@@ -10,8 +10,8 @@
 //   rmb_symx_coop.hip  workgroup-cooperative instances of the generic symmetric skeleton (launch thunks too)
 //   rmb_symx2t.hip, rmb_symx2t_per.hip  two-targets-per-lane instances of the generic skeleton, open / pseudo-periodic
 //   rmb_sort.hip     Morton ordering of the blobs for the force kernel's tile culling (rocPRIM radix sort)
-//   rmb_sweep.hip    launchers of the one-sided kernels: sweep, force sweep, source->target, pressure / double layer,
-//                    dense body blocks, position packing
+//   rmb_sweep.hip    the one-sided kernels (one frame, onesided_kernels.h; one launcher, one_sided_launch below): sweep,
+//                    force sweep, source->target, pressure / double layer; dense body blocks, position packing
 //   rmb_entry.hip    the extern "C" products: argument checks, routing between the two families, host staging
 //   rmb_multi.hip    the single-process multi-device engine (rmb_multi_*)
 //   rmb_rigid.hip    per-body geometry (positions, K) and the per-body factors of the block-diagonal preconditioner
@@ -179,6 +179,38 @@ rmb::PairConsts make_pair_consts(double a);
 rmb::ExpConsts exp_consts();
 void choose_chunks(long n_tgt, long n_src, long forced, long slots, long* n_chunks, long* chunk_len);
 int resident_blocks(const void* fn, int* cache);   // workgroups of 256 threads per CU, capped at 8
+// The launch of every one-sided sweep (onesided_kernels.h): chunk plan from the residency of this instance, workspace
+// of the chunk partials, bookkeeping, the sweep between the timing events, the finalize kernel when there are chunks.
+// `a` comes with the operator's own fields, n_src and the target range filled in.
+template <auto SWEEP, auto FINALIZE, int NOUT, class Args>
+int one_sided_launch(rmb_ctx* c, Args a) {
+  static int occ = 0;   // resident workgroups per CU of SWEEP
+  const long n_tgt = a.tgt_end - a.tgt_begin;
+  const long tiles = (n_tgt + 63) / 64;
+  const long slots = c->n_cu * resident_blocks((const void*)SWEEP, &occ);
+  long n_chunks, chunk_len;
+  choose_chunks(n_tgt, a.n_src, c->opt_chunks, slots, &n_chunks, &chunk_len);
+  if (tiles > 0x7fffffffL || n_chunks > 65535) return fail(RMB_ERR_ARG, "problem too large for one launch");
+  a.n_tgt_pad = 64 * tiles;
+  a.chunk_len = chunk_len;
+  a.n_chunks = (int)n_chunks;
+  a.partial = nullptr;
+  if (n_chunks > 1) {
+    if (int rc = c->partial.reserve((size_t)n_chunks * NOUT * a.n_tgt_pad * sizeof(double))) return rc;
+    a.partial = (double*)c->partial.p;
+  }
+  c->last_path = 0; c->last_tiles = tiles; c->last_chunks = n_chunks; c->last_wgs = tiles * n_chunks;
+  int slot;
+  if (int rc = timing_begin(c, &slot)) return rc;
+  hipLaunchKernelGGL(SWEEP, dim3((unsigned)tiles, (unsigned)n_chunks), dim3(rmb::kBlock), 0, c->stream, a);
+  RMB_HIP(hipGetLastError());
+  if (int rc = timing_end(c, slot)) return rc;
+  if (n_chunks > 1) {
+    hipLaunchKernelGGL(FINALIZE, dim3((unsigned)((n_tgt + 255) / 256)), dim3(256), 0, c->stream, a);
+    RMB_HIP(hipGetLastError());
+  }
+  return 0;
+}
 // Launch plan of a symmetric sweep: `total` rotation steps over `blocks` workgroups of 4 waves.
 struct SymPlan { long blocks; long steps_per_wave; size_t dyn_lds; bool sub_round; long round; };   // round: resident workgroups; sub_round: less work than that
 int plan_sym(rmb_ctx* c, const void* fn, int* occ_cache, size_t static_lds, long total, bool pin, SymPlan* out,

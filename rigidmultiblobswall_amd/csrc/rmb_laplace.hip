@@ -11,33 +11,9 @@ namespace rmbi {
 namespace {
 
 template <int OP, bool WALL, bool SELF>
-int laplace_launch(rmb_ctx* c, rmb::LapArgs a) {
-  typedef void (*lap_fn)(const rmb::LapArgs);
+int laplace_launch(rmb_ctx* c, const rmb::LapArgs& a) {
   constexpr int NOUT = rmb::LapShape<OP>::NOUT;
-  static int occ = 0;
-  lap_fn fn = (lap_fn)rmb::laplace_sweep_kernel<OP, WALL, SELF>;
-  const long tiles = (a.nt + 63) / 64;
-  a.n_tgt_pad = 64 * tiles;
-  const long slots = c->n_cu * resident_blocks((const void*)fn, &occ);
-  long n_chunks, chunk_len;
-  choose_chunks(a.nt, a.ns, c->opt_chunks, slots, &n_chunks, &chunk_len);
-  if (tiles > 0x7fffffffL || n_chunks > 65535) return fail(RMB_ERR_ARG, "problem too large for one launch");
-  a.chunk_len = chunk_len; a.n_chunks = (int)n_chunks; a.partial = nullptr;
-  if (n_chunks > 1) {
-    if (int rc = c->partial.reserve((size_t)n_chunks * NOUT * a.n_tgt_pad * sizeof(double))) return rc;
-    a.partial = (double*)c->partial.p;
-  }
-  c->last_path = 0; c->last_tiles = tiles; c->last_chunks = n_chunks; c->last_wgs = tiles * n_chunks;
-  int slot;
-  if (int rc = timing_begin(c, &slot)) return rc;
-  hipLaunchKernelGGL(fn, dim3((unsigned)tiles, (unsigned)n_chunks), dim3(rmb::kBlock), 0, c->stream, a);
-  RMB_HIP(hipGetLastError());
-  if (int rc = timing_end(c, slot)) return rc;
-  if (n_chunks > 1) {
-    hipLaunchKernelGGL(rmb::laplace_finalize_kernel<NOUT>, dim3((unsigned)((a.nt + 255) / 256)), dim3(256), 0, c->stream, a);
-    RMB_HIP(hipGetLastError());
-  }
-  return 0;
+  return one_sided_launch<rmb::laplace_sweep_kernel<OP, WALL, SELF>, rmb::laplace_finalize_kernel<NOUT>, NOUT>(c, a);
 }
 
 template <int OP, bool SELF>
@@ -51,7 +27,7 @@ int laplace_device(rmb_ctx* c, int op, bool self, long ns, const double* src, lo
                    int wall, double* out) {
   rmb::LapArgs a{};
   a.src = src; a.tgt = tgt; a.nrm = nrm; a.w = w; a.p = p; a.q = q; a.c = cfield; a.out = out;
-  a.ns = ns; a.nt = nt; a.sp = sp; a.sq = sq; a.alpha = alpha; a.prefactor = 1.0 / (4.0 * M_PI);
+  a.n_src = ns; a.tgt_end = nt; a.sp = sp; a.sq = sq; a.alpha = alpha; a.prefactor = 1.0 / (4.0 * M_PI);
   if (self) {
     switch (op) {
       case rmb::LAP_S: return laplace_wall<rmb::LAP_S, true>(c, a, wall);

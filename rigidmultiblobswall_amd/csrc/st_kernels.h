@@ -15,24 +15,19 @@
 //   delta = -2 y3 i3 + 2 (b2 - a2) y3 i5 + (20/3) a2 b2 rz i7
 //   eps   = -2 i1 - (2/3) s i3 - (4/3) a2 b2 i5
 // (a2 = a_t^2, b2 = a_s^2, s = a2 + b2, x3 / y3 = target / source height, rz = x3 + y3, i_n = |R|^-n).
-// Same sweep skeleton as matvec_kernels.h: lane = target, 4 waves split an LDS tile of sources, source
-// chunks over blockIdx.y, fixed-order reduction, atomic-free.  No self special case: r <= |a_t - a_s|
-// (which includes r = 0) is the third regime of the unbounded part.
+// A policy of the one-sided frame (onesided_kernels.h).  No self special case: r <= |a_t - a_s| (which includes r = 0)
+// is the third regime of the unbounded part.
 #pragma once
 #include "matvec_kernels.h"
 
 namespace rmb {
 
-struct StArgs {
-  const double4* src;   // [ns] (x, y, z_eff, b)
-  const double* rad_s;  // [ns]
-  const double* force;  // [3 ns]
-  const double4* tgt;   // [nt] (x, y, z_eff, b)
-  const double* rad_t;  // [nt]
-  double* out;          // [3 nt]
-  double* partial;      // [n_chunks][3][n_tgt_pad]
-  long ns, nt, n_tgt_pad, chunk_len;
-  int n_chunks;
+struct StArgs : OneSidedArgs {
+  const double4* src;   // [n_src] (x, y, z_eff, b)
+  const double* rad_s;  // [n_src]
+  const double* force;  // [3 n_src]
+  const double4* tgt;   // [tgt_end] (x, y, z_eff, b)
+  const double* rad_t;  // [tgt_end]
   double prefactor;
   double Lx, Ly, Lz, iLx, iLy, iLz;
 };
@@ -122,80 +117,50 @@ __device__ __forceinline__ void pair_st_mode(double dx, double dy, double dz, do
   if constexpr (MODE == 2) pair_st<false>(dx, dy, zt + zs, zt, zs, at, as, fx, fy, -fz, u);
 }
 
-template <int MODE, bool PERIODIC>
-__global__ __launch_bounds__(kBlock) void st_sweep_kernel(const StArgs a) {
-  __shared__ double2 tile[kTile * 4];
-  __shared__ double red[(kWaves - 1) * 3 * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const long ti = 64L * blockIdx.x + lane;
-  const bool valid = ti < a.nt;
-  const double4 tp = a.tgt[valid ? ti : a.nt - 1];
-  const double at = a.rad_t[valid ? ti : a.nt - 1];
-  const long c0 = (long)blockIdx.y * a.chunk_len;
-  long c1 = c0 + a.chunk_len;
-  if (c1 > a.ns) c1 = a.ns;
-  Vec3 acc = {0.0, 0.0, 0.0};
-  for (long j0 = c0; j0 < c1; j0 += kTile) {
-    const int n = (int)((c1 - j0 < kTile) ? (c1 - j0) : kTile);
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kBlock) {
-      const long j = j0 + t;
-      const double4 p = a.src[j];
-      tile[t * 4 + 0] = make_double2(p.x, p.y);
-      tile[t * 4 + 1] = make_double2(p.z, a.rad_s[j]);
-      tile[t * 4 + 2] = make_double2(a.force[3 * j] * p.w, a.force[3 * j + 1] * p.w);
-      tile[t * 4 + 3] = make_double2(a.force[3 * j + 2] * p.w, 0.0);
-    }
-    __syncthreads();
+template <int MODE, bool PERIODIC> struct StOp {
+  typedef StArgs Args;
+  struct Target { double4 p; double at; };
+  static constexpr int NOUT = 3, REC2 = 4;
+  static constexpr bool SHARDED = false, SKIP_OWN_TILE = false;
+
+  static __device__ __forceinline__ Target load_target(const Args& a, long t) { return {a.tgt[t], a.rad_t[t]}; }
+
+  static __device__ __forceinline__ void stage(const Args& a, long j, double2* rec) {
+    const double4 p = a.src[j];
+    rec[0] = make_double2(p.x, p.y);
+    rec[1] = make_double2(p.z, a.rad_s[j]);
+    rec[2] = make_double2(a.force[3 * j] * p.w, a.force[3 * j + 1] * p.w);
+    rec[3] = make_double2(a.force[3 * j + 2] * p.w, 0.0);
+  }
+
+  template <bool>
+  static __device__ __forceinline__ void tile_pairs(const Args& a, const double2* tile, int n, int wave, long, long,
+                                                    const Target& tg, double* out) {
+    const double4 tp = tg.p;
+    Vec3 acc = {out[0], out[1], out[2]};
     for (int s = wave; s < n; s += kWaves) {
       const double2 q0 = tile[s * 4 + 0], q1 = tile[s * 4 + 1], q2 = tile[s * 4 + 2], q3 = tile[s * 4 + 3];
-      double dx = tp.x - q0.x, dy = tp.y - q0.y, dz = tp.z - q1.x;
+      const double dx = tp.x - q0.x, dy = tp.y - q0.y, dz = tp.z - q1.x;
       if constexpr (!PERIODIC) {
-        pair_st_mode<MODE>(dx, dy, dz, tp.z, q1.x, at, q1.y, q2.x, q2.y, q3.x, acc);
+        pair_st_mode<MODE>(dx, dy, dz, tp.z, q1.x, tg.at, q1.y, q2.x, q2.y, q3.x, acc);
       } else {
-        const int px = a.Lx > 0, py = a.Ly > 0, pz = a.Lz > 0;
-        if (px) dx = wrap_nearest(dx, a.Lx, a.iLx);
-        if (py) dy = wrap_nearest(dy, a.Ly, a.iLy);
-        if (pz) dz = wrap_nearest(dz, a.Lz, a.iLz);
-        for (int bx = -px; bx <= px; ++bx)
-          for (int by = -py; by <= py; ++by)
-            for (int bz = -pz; bz <= pz; ++bz)
-              pair_st_mode<MODE>(dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, tp.z, q1.x, at, q1.y, q2.x, q2.y, q3.x, acc);
+        periodic_images(a, dx, dy, dz, [&](double ex, double ey, double ez, bool) {
+          pair_st_mode<MODE>(ex, ey, ez, tp.z, q1.x, tg.at, q1.y, q2.x, q2.y, q3.x, acc);
+        });
       }
     }
+    out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
   }
-  if (wave > 0) {
-    double* r = red + (wave - 1) * 3 * 64;
-    r[lane] = acc.x; r[64 + lane] = acc.y; r[128 + lane] = acc.z;
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 0; w < kWaves - 1; ++w) {
-    const double* r = red + w * 3 * 64;
-    acc.x += r[lane]; acc.y += r[64 + lane]; acc.z += r[128 + lane];
-  }
-  if (a.n_chunks == 1) {
-    if (!valid) return;
-    const double sc = a.prefactor * tp.w;
-    a.out[3 * ti] = acc.x * sc; a.out[3 * ti + 1] = acc.y * sc; a.out[3 * ti + 2] = acc.z * sc;
-  } else {
-    double* p = a.partial + (long)blockIdx.y * 3 * a.n_tgt_pad;
-    p[ti] = acc.x; p[a.n_tgt_pad + ti] = acc.y; p[2 * a.n_tgt_pad + ti] = acc.z;
-  }
-}
 
-__global__ __launch_bounds__(256) void st_finalize_kernel(const StArgs a) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nt) return;
-  double x = 0, y = 0, z = 0;
-  for (int c = 0; c < a.n_chunks; ++c) {
-    const double* p = a.partial + (long)c * 3 * a.n_tgt_pad;
-    x += p[t]; y += p[a.n_tgt_pad + t]; z += p[2 * a.n_tgt_pad + t];
+  static __device__ __forceinline__ void store(const Args& a, long t, const Target& tg, const double* acc) {
+    const double sc = a.prefactor * tg.p.w;
+    a.out[3 * t] = acc[0] * sc; a.out[3 * t + 1] = acc[1] * sc; a.out[3 * t + 2] = acc[2] * sc;
   }
-  const double sc = a.prefactor * a.tgt[t].w;
-  a.out[3 * t] = x * sc; a.out[3 * t + 1] = y * sc; a.out[3 * t + 2] = z * sc;
-}
+};
+
+template <int MODE, bool PERIODIC>
+__global__ __launch_bounds__(kBlock) void st_sweep_kernel(const StArgs a) { one_sided_sweep<StOp<MODE, PERIODIC>>(a); }
+
+__global__ __launch_bounds__(256) void st_finalize_kernel(const StArgs a) { one_sided_finalize<StOp<0, false>>(a); }
 
 }  // namespace rmb

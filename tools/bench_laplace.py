@@ -8,6 +8,7 @@ phoretic suspension, HIP events around the device work.
     the phoretic slip inside it (RHS + GMRES + gradient), its share, the Laplace and rigid GMRES iterations.
 
   python tools/bench_laplace.py [--out FILE.json] [--reps 5]
+  RMB_AB_LIB=<other build of librmb_mobility.so>   time that build instead (same-box A/B of two builds, as bench_ops.py)
 """
 import argparse
 import json
@@ -20,6 +21,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from rigidmultiblobswall_amd import _lib as _rmb_lib
+if os.environ.get("RMB_AB_LIB"):
+  _rmb_lib.LIB_PATH = os.path.abspath(os.environ["RMB_AB_LIB"])
 
 
 def _cloud(n, seed):
