@@ -113,6 +113,8 @@ int rmb_ctx_release_stream(rmb_ctx* ctx);
  *                          indices -- the culling then skips the same tile pairs whatever order the caller lists the blobs in
  *                          (262 144 rollers listed at random: 48 -> 4 ms).  Same pair terms in another summation order:
  *                          equal to rounding; 0 = keep the caller's order
+ *   "potential_resort" [16] rmb_blob_potential: rebuild the Morton permutation on every K-th evaluation and reuse it in
+ *                          between (see there)
  *   "force_precision" [0]  blob-blob forces: 0 = follow "precision", 32 / 64 = pinned whatever "precision" says
  *                          (products in single precision with double-precision forces, or the reverse)
  *   "det_workspace_mb" [8192]  workspace of mode 2; the unit list is processed in chunks that fit
@@ -376,6 +378,33 @@ int rmb_blob_blob_force(rmb_ctx* ctx, double repulsion_strength, double debye_le
                         double* out_host);
 int rmb_blob_blob_force_device(rmb_ctx* ctx, double repulsion_strength, double debye_length,
                                double blob_radius, double* out_dev);
+/* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
+ * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
+ * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:
+ * RMB_ERR_STATE); minimal image in x and y (periodic_length[2] is ignored, as in the reference); uniform radius, fp64.
+ *   form 0 "soft"    one blob, z > 0: weight z + (z < a ? e_w + e_w (a - z)/b_w : e_w exp(-(z - a)/b_w));
+ *                    pair: r < 2a ? e + e (2a - r)/b : e exp(-(r - 2a)/b)
+ *   form 1 "yukawa"  one blob: weight z + e_w a exp(-(z - a)/b_w)/|z - a| (+ 1e12 e_w when z < a); pair: e exp(-r/b)/r
+ *                    (many_bodyMCMC/examples/boomerang_suspension/potential_pycuda_user_defined.py:26-71; r = 0 gives inf)
+ * A blob with z <= 0 contributes 1e5 (1 - z) and no pair term as the lower of the caller's two indices.  repulsion_strength_wall
+ * = 0 drops the wall term (debye_length_wall is then not read).  Each unordered pair once, every lane its own fp64 sum, one
+ * partial per wave, a finishing launch that adds them in a fixed order: no atomics, bit-reproducible for a given
+ * configuration, permutation and option set.  Options "force_cull" (skip tile pairs beyond 2a + 750 b, yukawa 750 b: exact
+ * zeros) and "force_sort" (Morton order from 2048 blobs on) apply; "potential_resort" [K] = rebuild the Morton permutation on
+ * every K-th evaluation and reuse it in between (the tile bounds are recomputed every time, so any permutation is correct).
+ * The *_device variant writes the two doubles to device memory, asynchronously on the context's stream. */
+int rmb_blob_potential(rmb_ctx* ctx, double repulsion_strength, double debye_length, double repulsion_strength_wall,
+                       double debye_length_wall, double weight, double blob_radius, int form, double* out_host);
+int rmb_blob_potential_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double repulsion_strength_wall,
+                              double debye_length_wall, double weight, double blob_radius, int form, double* out_dev);
+/* One Metropolis proposal of the rigid-body sampler in one launch (many_bodyMCMC/many_body_MCMC.py:160-169): for body
+ * k < n_free  loc_new = loc + draws[k, 0:3],  quat_new = quaternion(draws[k, 3:6] max_angle_shift) * quat  (quaternion.py:17-39);
+ * bodies from n_free on (prescribed kinematics) keep theirs; then r_new = R(quat_new) ref + loc_new for every blob.
+ * blob_body_dev[n_blobs]: body of every blob (non-decreasing); blob_ref_dev[n_blobs]: row of ref_dev (rows x 3, the
+ * structures' reference configurations) of every blob; draws_dev (n_bodies, 6).  Outputs must not alias the inputs. */
+int rmb_mcmc_propose_device(rmb_ctx* ctx, long n_bodies, long n_free, long n_blobs, const int* blob_body_dev, const int* blob_ref_dev,
+                            const double* ref_dev, const double* loc_dev, const double* quat_dev, const double* draws_dev,
+                            double max_angle_shift, double* loc_new_dev, double* quat_new_dev, double* r_new_dev);
 /* One-blob forces of the rigid-multiblob driver (multi_bodies/multi_bodies_functions.py:153-188, `blob_external_force`):
  * f = (0, 0, -weight + wall repulsion), wall repulsion = (eps_wall / debye_wall) exp(-(h - a) / debye_wall) above contact
  * (h > a), eps_wall / debye_wall below; r_dev: n x 3 raw coordinates (the caller's, not the resident ones); accumulate != 0
@@ -479,6 +508,10 @@ int rmb_mobility_oneshot(int kind, int wall, int in_plane, long n, const double*
                          const double* vec2, double eta, double a, const double* L, double* out);
 int rmb_forces_oneshot(long n, const double* r, const double* L, double repulsion_strength,
                        double debye_length, double blob_radius, double* out);
+/* many_body_potential_pycuda.blobs_potential's arguments (r host (n,3), L = periodic_length or NULL): out = {U_one_blob, U_pair} */
+int rmb_potential_oneshot(long n, const double* r, const double* L, double repulsion_strength, double debye_length,
+                          double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
+                          double* out);
 
 /* ---- source -> target products with per-blob radii (K13) --------------------------------------
  * u_t = sum_s M(x_t, a_t; y_s, a_s) f_s for nt targets and ns sources, each blob with its own radius

@@ -7,6 +7,7 @@ Layout (only what the hot path needs):
   context.py    persistent per-GPU context (resident positions, host + device entry points)
   mobility.py   the reference's mobility/mobility.py function surface, `<impl> = hip`
   forces.py     calc_blob_blob_forces_hip
+  potential.py  blobs_potential_hip / compute_total_energy_hip (the many_bodyMCMC energy surface)
   distributed.py  pair / target sharding over torch.distributed (RCCL) + ReplicatedContext for the callers
 callers built on the path, each mirroring the reference module of the same role:
   rigid.py             RigidSuspension: saddle-point operator, block-diagonal preconditioner, GMRES
@@ -16,6 +17,7 @@ callers built on the path, each mirroring the reference module of th
   utilities.py         one-shot mobility / resistance / body_mobility problems, velocity field
   read_input.py, structures.py, dispatch.py   decks, .vertex / .clones / .slip files, backend strings
   __main__.py          python -m rigidmultiblobswall_amd --input-file deck
+  mcmc.py              MCMCSampler: Metropolis sampler of rigid-body configurations, python -m rigidmultiblobswall_amd.mcmc deck
 """
 from . import _lib  # noqa: F401
 from .context import MobilityContext  # noqa: F401

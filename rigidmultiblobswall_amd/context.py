@@ -22,6 +22,9 @@ def _ptr(x):
   return ctypes.c_void_p(x.ctypes.data)
 
 
+POTENTIAL_FORMS = {"soft": 0, "yukawa": 1}   # rmb_blob_potential's `form`
+
+
 class MobilityContext(object):
   """One context = one GPU.  Host (numpy) and device (torch tensor) entry points."""
 
@@ -475,6 +478,58 @@ class MobilityContext(object):
     _lib.check(self._lib.rmb_blob_blob_force_device(self._h, float(repulsion_strength), float(debye_length),
                                                     float(blob_radius), ctypes.c_void_p(out.data_ptr())))
     return out
+
+  def _potential_args(self, repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential):
+    if potential not in POTENTIAL_FORMS:
+      raise ValueError("potential must be one of %s, got %r" % (sorted(POTENTIAL_FORMS), potential))
+    eps_w = float(repulsion_strength_wall or 0.0)
+    return (float(repulsion_strength), float(debye_length), eps_w, float(debye_length_wall) if eps_w != 0.0 else 1.0, float(weight),
+            float(blob_radius), POTENTIAL_FORMS[potential])
+
+  def blob_potential(self, repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0,
+                     potential="soft"):
+    """(U_one_blob, U_pair) of the resident raw positions (set_positions(..., wall=False)): the equilibrium sampler's energy,
+    many_body_potential_pycuda.py:15-119 ("soft") or the boomerang example's Yukawa form ("yukawa"); rmb_blob_potential."""
+    out = np.empty(2)
+    _lib.check(self._lib.rmb_blob_potential(self._h, *self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall,
+                                                                          debye_length_wall, weight, blob_radius, potential), _ptr(out)))
+    return float(out[0]), float(out[1])
+
+  def blob_potential_device(self, repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0,
+                            weight=0.0, potential="soft", out=None, device=None):
+    """The same two sums as a CUDA float64 tensor of two entries, asynchronous on the context's stream
+    (rmb_blob_potential_device).  A caller's out= goes straight to the kernel."""
+    import torch
+    args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
+    if out is None:
+      out = torch.empty(2, dtype=torch.float64, device=device or ("cuda:%d" % self.device))
+    elif not _is_torch_cuda(out) or not out.is_contiguous() or out.numel() != 2:
+      raise ValueError("out must be a contiguous CUDA float64 tensor with 2 entries")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_blob_potential_device(self._h, *args, ctypes.c_void_p(out.data_ptr())))
+    return out
+
+  def mcmc_propose_device(self, blob_body, blob_ref, ref, loc, quat, draws, n_free, max_angle_shift, loc_new, quat_new, r_new):
+    """One Metropolis proposal for every body and the proposed blob coordinates in one launch (rmb_mcmc_propose_device)."""
+    import torch
+    for name, t in (("blob_body", blob_body), ("blob_ref", blob_ref)):
+      if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous CUDA int32 tensor" % name)
+    for name, t in (("ref", ref), ("loc", loc), ("quat", quat), ("draws", draws), ("loc_new", loc_new), ("quat_new", quat_new), ("r_new", r_new)):
+      if not _is_torch_cuda(t) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous CUDA float64 tensor" % name)
+    nb, n_blobs = loc.numel() // 3, blob_body.numel()
+    sizes = (("blob_ref", blob_ref, n_blobs), ("loc", loc, 3 * nb), ("quat", quat, 4 * nb), ("draws", draws, 6 * nb), ("loc_new", loc_new, 3 * nb),
+             ("quat_new", quat_new, 4 * nb), ("r_new", r_new, 3 * n_blobs))
+    for name, t, size in sizes:
+      if t.numel() != size:
+        raise ValueError("%s must have %d entries, has %d" % (name, size, t.numel()))
+    if ref.numel() % 3 or not 0 <= int(n_free) <= nb:
+      raise ValueError("ref must be (rows, 3) and 0 <= n_free <= n_bodies")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_mcmc_propose_device(self._h, nb, int(n_free), n_blobs, p(blob_body), p(blob_ref), p(ref), p(loc), p(quat), p(draws),
+                                                 float(max_angle_shift), p(loc_new), p(quat_new), p(r_new)))
 
   def one_blob_force_device(self, r, blob_radius, weight, eps_wall, debye_wall, out=None):
     """(0, 0, -weight + wall repulsion) per blob on the caller's coordinates r (n x 3 CUDA tensor; rmb_one_blob_force_device);

@@ -124,7 +124,7 @@ int rmb_ctx_destroy(rmb_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   rmbi::gmres_release(c);
-  c->wave_clock.release(); c->tile_bounds.release(); c->fpos.release(); c->fperm.release(); c->fsort_keys.release(); c->fsort_vals.release(); c->fsort_tmp.release(); c->fsort_box.release(); for (auto& b : c->st) b.release(); c->symbuf.release(); if (c->host_out) { (void)hipHostFree(c->host_out); c->host_out = nullptr; c->host_out_cap = 0; } if (c->host_in) { (void)hipHostFree(c->host_in); c->host_in = nullptr; c->host_in_cap = 0; } c->pos.release(); c->r_stage.release(); c->vec.release(); c->vec2.release(); c->out.release(); c->partial.release(); c->tmp3n.release(); c->det_ws.release(); c->krylov.release();
+  c->wave_clock.release(); c->pot_ws.release(); c->tile_bounds.release(); c->fpos.release(); c->fperm.release(); c->fsort_keys.release(); c->fsort_vals.release(); c->fsort_tmp.release(); c->fsort_box.release(); for (auto& b : c->st) b.release(); c->symbuf.release(); if (c->host_out) { (void)hipHostFree(c->host_out); c->host_out = nullptr; c->host_out_cap = 0; } if (c->host_in) { (void)hipHostFree(c->host_in); c->host_in = nullptr; c->host_in_cap = 0; } c->pos.release(); c->r_stage.release(); c->vec.release(); c->vec2.release(); c->out.release(); c->partial.release(); c->tmp3n.release(); c->det_ws.release(); c->krylov.release();
   if (c->stream_switch) (void)hipEventDestroy(c->stream_switch);
   for (auto e : c->ev0) (void)hipEventDestroy(e);
   for (auto e : c->ev1) (void)hipEventDestroy(e);
@@ -192,6 +192,7 @@ int rmb_ctx_set_option(rmb_ctx* c, const char* key, long value) {
   }
   if (!strcmp(key, "force_cull")) { c->opt_force_cull = value ? 1 : 0; return 0; }
   if (!strcmp(key, "force_sort")) { c->opt_force_sort = value ? 1 : 0; return 0; }
+  if (!strcmp(key, "potential_resort")) { c->opt_potential_resort = value < 1 ? 1 : value; c->pot_sort_age = -1; return 0; }
   if (!strcmp(key, "force_precision")) {
     if (value != 0 && value != 32 && value != 64) return fail(RMB_ERR_ARG, "force_precision must be 0 (follow \"precision\"), 32 or 64");
     c->opt_force_precision = value;
@@ -225,7 +226,7 @@ int rmb_ctx_get_option(rmb_ctx* c, const char* key, long* value) {
       {"fused_symmetric", &c->opt_fused_symmetric}, {"symx_single", &c->opt_symx_single},
       {"deterministic", &c->opt_deterministic}, {"det_workspace_mb", &c->opt_det_workspace_mb}, {"sym_wps", &c->opt_sym_wps},
       {"wave_clock", &c->opt_wave_clock}, {"skip_pairs", &c->opt_skip_pairs}, {"sym_pin", &c->opt_sym_pin},
-      {"precision", &c->opt_precision}, {"force_precision", &c->opt_force_precision}, {"force_cull", &c->opt_force_cull}, {"force_sort", &c->opt_force_sort}, {"sym_oversub", &c->opt_sym_oversub}, {"sym_fine_steps", &c->opt_sym_fine_steps}, {"sym_coop", &c->opt_sym_coop}, {"sym_order", &c->opt_sym_order}, {"host_zero_copy", &c->opt_host_zero_copy}, {"host_zero_copy_in", &c->opt_host_zero_copy_in}, {"gmres_fuse_pc", &c->opt_gmres_fuse_pc}, {"gmres_fuse_dots", &c->opt_gmres_fuse_dots}, {"krylov_low_sync", &c->opt_krylov_low_sync}, {"lanczos_fuse_finish", &c->opt_lanczos_fuse_finish}, {"sym_two_targets", &c->opt_sym_two_targets}, {"sym_chunk_steps", &c->opt_sym_chunk_steps}, {"sym_xcd", &c->opt_sym_xcd},
+      {"precision", &c->opt_precision}, {"force_precision", &c->opt_force_precision}, {"force_cull", &c->opt_force_cull}, {"force_sort", &c->opt_force_sort}, {"potential_resort", &c->opt_potential_resort}, {"sym_oversub", &c->opt_sym_oversub}, {"sym_fine_steps", &c->opt_sym_fine_steps}, {"sym_coop", &c->opt_sym_coop}, {"sym_order", &c->opt_sym_order}, {"host_zero_copy", &c->opt_host_zero_copy}, {"host_zero_copy_in", &c->opt_host_zero_copy_in}, {"gmres_fuse_pc", &c->opt_gmres_fuse_pc}, {"gmres_fuse_dots", &c->opt_gmres_fuse_dots}, {"krylov_low_sync", &c->opt_krylov_low_sync}, {"lanczos_fuse_finish", &c->opt_lanczos_fuse_finish}, {"sym_two_targets", &c->opt_sym_two_targets}, {"sym_chunk_steps", &c->opt_sym_chunk_steps}, {"sym_xcd", &c->opt_sym_xcd},
       {"sym_min_steps", &c->opt_sym_min_steps}};
   // read-only: which kernel family the last product ran on (0 one-sided sweep, 1 symmetric per-wave, 2 deterministic
   // symmetric, 3 symmetric workgroup-cooperative)
@@ -247,7 +248,7 @@ int rmb_ctx_get_option(rmb_ctx* c, const char* key, long* value) {
     mix(c->pos); mix(c->r_stage); mix(c->vec); mix(c->vec2); mix(c->out); mix(c->partial); mix(c->tmp3n); mix(c->tile_bounds);
     mix(c->fpos); mix(c->fperm); mix(c->fsort_keys); mix(c->fsort_vals); mix(c->fsort_tmp); mix(c->fsort_box); mix(c->det_ws);
     for (const auto& b : c->st) mix(b);
-    mix(c->wave_clock); mix(c->krylov); mix(c->symbuf);
+    mix(c->wave_clock); mix(c->pot_ws); mix(c->krylov); mix(c->symbuf);
     *value = (long)(h >> 1);
     return 0;
   }

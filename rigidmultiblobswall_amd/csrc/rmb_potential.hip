@@ -1,0 +1,197 @@
+// rmb_potential.hip -- total potential energy of the resident blob configuration (potential_kernels.h) and the Metropolis
+// proposal of the equilibrium sampler (many_bodyMCMC/many_body_potential_pycuda.py, many_body_MCMC.py:158-169).
+#include "rmb_internal.h"
+
+#include <cmath>
+#include <limits>
+
+#include "potential_kernels.h"
+
+namespace rmbi {
+namespace {
+
+typedef void (*potential_fn)(const rmb::PotentialArgs);
+
+// The sweep + the finishing launch on the context's stream; the two sums end up in out_dev[0..1].
+int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
+                          double* out_dev) {
+  if (int rc = check_ready(c)) return rc;
+  if (!out_dev) return fail(RMB_ERR_ARG, "null output pointer");
+  if (form != rmb::POT_SOFT && form != rmb::POT_YUKAWA) return fail(RMB_ERR_ARG, "potential form must be 0 (soft) or 1 (yukawa)");
+  if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
+  if (eps_wall != 0.0 && !(b_wall > 0.0)) return fail(RMB_ERR_ARG, "debye_length_wall must be positive when repulsion_strength_wall is not zero");
+  if (c->wall) return fail(RMB_ERR_STATE, "the potential uses raw heights: call rmb_set_positions with wall = 0");
+  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the potential is a sum over all blobs: reset the target range");
+  RMB_HIP(hipSetDevice(c->device));
+  const long n = c->n, tiles = (n + 63) / 64;
+  if (n == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, 2 * sizeof(double), c->stream)); return 0; }
+  if (n > 0xffffffffL) return fail(RMB_ERR_ARG, "potential: more than 2^32 blobs");
+
+  rmb::PotentialArgs a;
+  a.pos = (const double4*)c->pos.p;
+  a.perm = nullptr;
+  a.n = n; a.n_tiles = (int)tiles;
+  a.order = 0; a.xcd = 0;      // as the force sweep (rmb_sym.hip): after culling the surviving units hug the diagonal
+  a.step_end = tiles * (tiles + 1) / 2 * 64;
+  a.Lx = c->L[0]; a.Ly = c->L[1];                 // x and y only: the reference ignores periodic_length[2]
+  a.iLx = a.Lx > 0 ? 1.0 / a.Lx : 0.0; a.iLy = a.Ly > 0 ? 1.0 / a.Ly : 0.0;
+  const bool periodic = a.Lx > 0 || a.Ly > 0;
+  a.eps = eps; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
+  a.eps_wall = eps_wall; a.inv_b_wall = eps_wall != 0.0 ? 1.0 / b_wall : 0.0; a.a = blob_radius; a.weight = weight;
+  a.ec = exp_consts();
+
+  // Spatial order and tile bounds.  The bounds are recomputed for every evaluation (the culling is correct for ANY
+  // order); the Morton permutation is kept and rebuilt on every "potential_resort"-th evaluation.
+  const bool sorted = c->opt_force_sort && tiles >= 32;
+  bool rebuild = true;
+  if (sorted) {
+    rebuild = c->fperm_n != n || c->pot_sort_age < 0 || c->pot_sort_age + 1 >= c->opt_potential_resort;
+    if (rebuild) {
+      if (int rc = force_sort_positions(c)) return rc;
+      c->pot_sort_age = 0;
+    } else {
+      if (int rc = force_regather_positions(c)) return rc;
+      ++c->pot_sort_age;
+    }
+    a.pos = (const double4*)c->fpos.p;
+    a.perm = (const unsigned*)c->fperm.p;
+  } else {
+    if (int rc = c->tile_bounds.reserve((size_t)6 * tiles * sizeof(double))) return rc;
+    hipLaunchKernelGGL(rmb::tile_bounds_kernel, dim3((unsigned)tiles), dim3(64), 0, c->stream, (const double4*)c->pos.p, n,
+                       (double*)c->tile_bounds.p);
+    RMB_HIP(hipGetLastError());
+  }
+  // What the force path finds (rmb_sym.hip): after a full sort, or bounds in the caller's order, exactly what it would have
+  // built itself for this configuration -- it may use them; a sorted copy along a REUSED permutation is correct too, but
+  // not the order the forces alone would sum in, so the force path is told to build its own.
+  c->tile_bounds_valid = rebuild;
+  c->force_sorted = sorted;
+  a.bounds = (const double*)c->tile_bounds.p;
+  const double reach = form == rmb::POT_SOFT ? 2.0 * blob_radius + 750.0 * b : 750.0 * b;
+  a.cull2 = c->opt_force_cull ? reach * reach : std::numeric_limits<double>::infinity();
+
+  static int occ[2][2] = {{0, 0}, {0, 0}};
+  const potential_fn fn = form == rmb::POT_SOFT
+                              ? (periodic ? (potential_fn)rmb::potential_kernel<rmb::POT_SOFT, true> : (potential_fn)rmb::potential_kernel<rmb::POT_SOFT, false>)
+                              : (periodic ? (potential_fn)rmb::potential_kernel<rmb::POT_YUKAWA, true>
+                                          : (potential_fn)rmb::potential_kernel<rmb::POT_YUKAWA, false>);
+  long blocks = c->n_cu * resident_blocks((const void*)fn, &occ[form][periodic ? 1 : 0]) * c->opt_sym_oversub;
+  const long need = (a.step_end + 255) / 256;
+  if (blocks > need) blocks = need;
+  if (blocks < 1) blocks = 1;
+  const long waves = blocks * rmb::kSymWaves;
+  {
+    const long spw = (a.step_end + waves - 1) / waves;
+    const long ch = chunked_steps(c, a.step_end, waves, spw, c->opt_sym_chunk_steps / 4);
+    a.chunk_steps = ch < spw ? ch : 0;
+  }
+  if (int rc = c->pot_ws.reserve((size_t)(2 * waves + 2) * sizeof(double))) return rc;
+  a.partial = (double*)c->pot_ws.p;
+  a.n_partial = waves;
+  a.out = out_dev;
+  c->last_path = 1; c->last_tiles = tiles; c->last_chunks = 0; c->last_wgs = blocks;
+  int slot;
+  if (int rc = timing_begin(c, &slot)) return rc;
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64 * rmb::kSymWaves), 0, c->stream, a);
+  RMB_HIP(hipGetLastError());
+  if (int rc = timing_end(c, slot)) return rc;       // the sweep alone, as the force path brackets its own
+  hipLaunchKernelGGL(rmb::potential_finish_kernel, dim3(1), dim3(256), 0, c->stream, a);
+  RMB_HIP(hipGetLastError());
+  return 0;
+}
+
+struct ProposeArgs {
+  long n_bodies, n_free, n_blobs;
+  const int* blob_body;   // [n_blobs] body of every blob (bodies in order)
+  const int* blob_ref;    // [n_blobs] row of `ref` that is this blob's body-frame position
+  const double* ref;      // (rows, 3) reference configurations of every structure
+  const double *loc, *quat, *draws;
+  double max_angle_shift;
+  double *loc_new, *quat_new, *r_new;
+};
+
+// many_body_MCMC.py:160-169 for every body at once: x' = x + du, q' = quaternion(dphi) q (quaternion.py:17-39), bodies from
+// n_free on keep theirs; r = R(q') ref + x' for every blob (body.py:64-78).  One thread per blob; the first blob of a
+// body also stores the body's proposal.
+__global__ __launch_bounds__(256) void mcmc_propose_kernel(const ProposeArgs a) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= a.n_blobs) return;
+  const long b = a.blob_body[id];
+  double x = a.loc[3 * b], y = a.loc[3 * b + 1], z = a.loc[3 * b + 2];
+  double s = a.quat[4 * b], p0 = a.quat[4 * b + 1], p1 = a.quat[4 * b + 2], p2 = a.quat[4 * b + 3];
+  if (b < a.n_free) {
+    const double* d = a.draws + 6 * b;
+    x += d[0]; y += d[1]; z += d[2];
+    const double px = d[3] * a.max_angle_shift, py = d[4] * a.max_angle_shift, pz = d[5] * a.max_angle_shift;
+    const double nrm = sqrt(px * px + py * py + pz * pz);
+    const double qs = cos(0.5 * nrm), f = nrm != 0.0 ? sin(0.5 * nrm) / nrm : 0.0;
+    const double qx = f * px, qy = f * py, qz = f * pz;
+    const double ns = qs * s - (qx * p0 + qy * p1 + qz * p2);
+    const double n0 = qs * p0 + s * qx + (qy * p2 - qz * p1);
+    const double n1 = qs * p1 + s * qy + (qz * p0 - qx * p2);
+    const double n2 = qs * p2 + s * qz + (qx * p1 - qy * p0);
+    s = ns; p0 = n0; p1 = n1; p2 = n2;
+  }
+  if (id == 0 || a.blob_body[id - 1] != b) {
+    a.loc_new[3 * b] = x; a.loc_new[3 * b + 1] = y; a.loc_new[3 * b + 2] = z;
+    a.quat_new[4 * b] = s; a.quat_new[4 * b + 1] = p0; a.quat_new[4 * b + 2] = p1; a.quat_new[4 * b + 3] = p2;
+  }
+  const double* rf = a.ref + 3L * a.blob_ref[id];
+  const double d = s * s - 0.5;
+  const double rx = 2.0 * ((p0 * p0 + d) * rf[0] + (p0 * p1 - s * p2) * rf[1] + (p0 * p2 + s * p1) * rf[2]);
+  const double ry = 2.0 * ((p1 * p0 + s * p2) * rf[0] + (p1 * p1 + d) * rf[1] + (p1 * p2 - s * p0) * rf[2]);
+  const double rz = 2.0 * ((p2 * p0 - s * p1) * rf[0] + (p2 * p1 + s * p0) * rf[1] + (p2 * p2 + d) * rf[2]);
+  a.r_new[3 * id] = rx + x; a.r_new[3 * id + 1] = ry + y; a.r_new[3 * id + 2] = rz + z;
+}
+
+}  // namespace
+}  // namespace rmbi
+
+using rmbi::fail;
+
+extern "C" {
+
+int rmb_blob_potential_device(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
+                              double* out_dev) {
+  return rmbi::potential_device_impl(c, eps, b, eps_wall, b_wall, weight, blob_radius, form, out_dev);
+}
+
+int rmb_blob_potential(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
+                       double* out) {
+  if (int rc = rmbi::check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  if (int rc = c->out.reserve(2 * sizeof(double))) return rc;
+  if (int rc = rmbi::potential_device_impl(c, eps, b, eps_wall, b_wall, weight, blob_radius, form, (double*)c->out.p)) return rc;
+  RMB_HIP(hipMemcpyAsync(out, c->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  RMB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int rmb_potential_oneshot(long n, const double* r, const double* L, double eps, double b, double eps_wall, double b_wall, double weight,
+                          double blob_radius, int form, double* out) {
+  std::lock_guard<std::mutex> lk(rmbi::g_default_mu);
+  rmb_ctx* c;
+  if (int rc = rmbi::default_ctx(&c)) return rc;
+  if (int rc = rmb_set_positions(c, r, n, blob_radius, L, 0)) return rc;
+  return rmb_blob_potential(c, eps, b, eps_wall, b_wall, weight, blob_radius, form, out);
+}
+
+int rmb_mcmc_propose_device(rmb_ctx* c, long n_bodies, long n_free, long n_blobs, const int* blob_body_dev, const int* blob_ref_dev,
+                            const double* ref_dev, const double* loc_dev, const double* quat_dev, const double* draws_dev,
+                            double max_angle_shift, double* loc_new_dev, double* quat_new_dev, double* r_new_dev) {
+  if (!c) return fail(RMB_ERR_ARG, "null context");
+  if (n_bodies < 0 || n_blobs < 0 || n_free < 0 || n_free > n_bodies) return fail(RMB_ERR_ARG, "rmb_mcmc_propose_device: bad sizes");
+  if (n_blobs == 0) return 0;
+  if (!blob_body_dev || !blob_ref_dev || !ref_dev || !loc_dev || !quat_dev || !loc_new_dev || !quat_new_dev || !r_new_dev ||
+      (n_free > 0 && !draws_dev))
+    return fail(RMB_ERR_ARG, "rmb_mcmc_propose_device: null pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  rmbi::ProposeArgs a{n_bodies, n_free, n_blobs, blob_body_dev, blob_ref_dev, ref_dev, loc_dev, quat_dev, draws_dev, max_angle_shift,
+                      loc_new_dev, quat_new_dev, r_new_dev};
+  hipLaunchKernelGGL(rmbi::mcmc_propose_kernel, dim3((unsigned)((n_blobs + 255) / 256)), dim3(256), 0, c->stream, a);
+  RMB_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

@@ -136,6 +136,21 @@ int force_sort_positions(rmb_ctx* c) {
                      (double4*)c->fpos.p);
   hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)tiles), dim3(64), 0, c->stream, (const double4*)c->fpos.p, n, (double*)c->tile_bounds.p);
   RMB_HIP(hipGetLastError());
+  c->fperm_n = n;
+  return 0;
+}
+
+// The sorted copy and its tile bounds for the resident configuration with the permutation fperm ALREADY holds (any
+// permutation of the n blobs is a correct one: the culling reads only the bounds, which are recomputed here).
+int force_regather_positions(rmb_ctx* c) {
+  const long n = c->n, tiles = (n + 63) / 64;
+  if (c->fperm_n != n) return fail(RMB_ERR_STATE, "force_regather_positions: no permutation of this many blobs");
+  if (int rc = c->tile_bounds.reserve((size_t)6 * tiles * sizeof(double))) return rc;
+  if (int rc = c->fpos.reserve((size_t)n * sizeof(double4))) return rc;
+  hipLaunchKernelGGL(gather_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double4*)c->pos.p,
+                     (const unsigned*)c->fperm.p, n, (double4*)c->fpos.p);
+  hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)tiles), dim3(64), 0, c->stream, (const double4*)c->fpos.p, n, (double*)c->tile_bounds.p);
+  RMB_HIP(hipGetLastError());
   return 0;
 }
 

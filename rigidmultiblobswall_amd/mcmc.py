@@ -1,0 +1,340 @@
+"""Metropolis sampler of rigid-body configurations -- many_bodyMCMC/many_body_MCMC.py on MI355X.
+
+    python -m rigidmultiblobswall_amd.mcmc [inputfile] [--device N] [--potential soft|yukawa] [--rng reference|batched]
+
+Same decks, same outputs (.inputfile, .random_state, .clones per saved step or one appended .config, .time, .MCMC_info)
+and, with rng="reference", the same chain as the reference script for the same seed: the draws come from a
+numpy.random.RandomState in the reference's call order (per free body uniform(3) then normal(3); one uniform per step).
+The legacy generator caches a Gaussian between calls, so that interleaving cannot be vectorised and the per-body loop of
+draws stays on the host; rng="batched" draws one (n, 3) uniform and one (n, 3) normal block per step -- the same
+distribution on another stream, for large decks.
+
+State on the device: body locations, quaternions and the structures' reference configurations.  Per step the host
+uploads one (n_bodies, 6) array of draws, one launch composes the proposal and writes the proposed blob coordinates
+(rmb_mcmc_propose_device), the energy sweep runs (rmb_blob_potential), one pair of doubles comes back; an accepted
+proposal becomes current by swapping the two sets of tensors.
+
+`MCMCSampler(..., energy=f)` runs the same chain with f(r_vectors) -> float as the energy and numpy state instead (the
+host tests replay the reference's fixtures with the numpy restatement that way); without it the energy is the HIP one --
+there is no silent fall-back in either direction.
+"""
+import argparse
+import os
+import shutil
+import sys
+import time
+
+import numpy as np
+
+from .read_input import ReadInput
+from .structures import read_clones_file, read_vertex_file
+
+USER_POTENTIAL_FILE = "potential_pycuda_user_defined.py"
+
+
+class UserDefinedPotentialError(RuntimeError):
+  pass
+
+
+def refuse_user_defined_potential(directory="."):
+  """The reference swaps its potential module for `potential_pycuda_user_defined.py` when that file lies in the working
+  directory (many_body_MCMC.py:35-43).  A CUDA string cannot run here, and sampling another potential without saying so
+  is the one thing a sampler must not do."""
+  path = os.path.join(directory, USER_POTENTIAL_FILE)
+  if os.path.isfile(path):
+    raise UserDefinedPotentialError(
+        "%s found: CUDA-string potentials are not supported by the HIP sampler.  The Yukawa potential of the reference's "
+        "boomerang_suspension example is built in: run with --potential yukawa (MCMCSampler(potential='yukawa')) from a "
+        "directory without that file; any other user-defined potential is not implemented." % path)
+
+
+def body_length(reference_configuration, blob_radius):
+  """Body.calc_body_length (body/body.py:218-231): the furthest blob pair plus 2a."""
+  r = np.asarray(reference_configuration, dtype=np.float64)[:, :3]
+  d = np.linalg.norm(r[:, None, :] - r[None, :, :], axis=-1)
+  return float(d.max()) + 2.0 * blob_radius
+
+
+def rotation_matrices(quat):
+  """(n, 3, 3) rotation matrices of unit quaternions (s, p) (quaternion.py:42-51)."""
+  s, p = quat[:, 0], quat[:, 1:]
+  diag = s * s - 0.5
+  R = p[:, :, None] * p[:, None, :]
+  R[:, 0, 0] += diag; R[:, 1, 1] += diag; R[:, 2, 2] += diag
+  R[:, 0, 1] -= s * p[:, 2]; R[:, 0, 2] += s * p[:, 1]
+  R[:, 1, 0] += s * p[:, 2]; R[:, 1, 2] -= s * p[:, 0]
+  R[:, 2, 0] -= s * p[:, 1]; R[:, 2, 1] += s * p[:, 0]
+  return 2.0 * R
+
+
+def compose_proposal(loc, quat, draws, n_free, max_angle_shift):
+  """numpy twin of rmb_mcmc_propose_device's first half: (loc_new, quat_new)."""
+  loc_new, quat_new = loc.copy(), quat.copy()
+  if n_free:
+    loc_new[:n_free] += draws[:n_free, 0:3]
+    phi = draws[:n_free, 3:6] * max_angle_shift
+    nrm = np.linalg.norm(phi, axis=1)
+    qs = np.cos(0.5 * nrm)
+    with np.errstate(invalid="ignore", divide="ignore"):
+      qp = np.where(nrm[:, None] != 0, np.sin(0.5 * nrm)[:, None] * (phi / nrm[:, None]), 0.0)
+    s, p = quat[:n_free, 0], quat[:n_free, 1:]
+    quat_new[:n_free, 0] = qs * s - np.einsum("ij,ij->i", qp, p)
+    quat_new[:n_free, 1:] = qs[:, None] * p + s[:, None] * qp + np.cross(qp, p)
+  return loc_new, quat_new
+
+
+class _HostState(object):
+  """Bodies as numpy arrays; the energy is the caller's function of the blob coordinates."""
+
+  def __init__(self, sampler, energy):
+    self.s, self.energy_fn = sampler, energy
+    self.loc, self.quat = sampler.loc0.copy(), sampler.quat0.copy()
+
+  def _blobs(self, loc, quat):
+    s = self.s
+    R = rotation_matrices(quat)
+    return np.einsum("bij,bj->bi", R[s.blob_body], s.ref_all[s.blob_ref]) + loc[s.blob_body]
+
+  def current_energy(self):
+    return self.energy_fn(self._blobs(self.loc, self.quat))
+
+  def propose(self, draws, max_angle_shift):
+    self.loc_new, self.quat_new = compose_proposal(self.loc, self.quat, draws, self.s.n_free, max_angle_shift)
+    return self.energy_fn(self._blobs(self.loc_new, self.quat_new))
+
+  def accept(self):
+    self.loc, self.quat = self.loc_new, self.quat_new
+
+  def configuration(self):
+    return self.loc, self.quat
+
+  def close(self):
+    pass
+
+
+class _DeviceState(object):
+  """Bodies as CUDA tensors; proposal and energy are HIP launches on one context."""
+
+  def __init__(self, sampler, device):
+    import torch
+    from .context import MobilityContext
+    self.torch, self.s = torch, sampler
+    self.dev = torch.device("cuda", int(device))
+    self.ctx = MobilityContext(int(device))
+    t = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt).to(self.dev)   # noqa: E731
+    self.loc, self.quat = t(sampler.loc0), t(sampler.quat0)
+    self.loc_new, self.quat_new = torch.empty_like(self.loc), torch.empty_like(self.quat)
+    self.ref = t(sampler.ref_all)
+    self.blob_body, self.blob_ref = t(sampler.blob_body, torch.int32), t(sampler.blob_ref, torch.int32)
+    self.r_new = torch.empty((sampler.n_blobs, 3), dtype=torch.float64, device=self.dev)
+    self.draws_host = torch.zeros((sampler.n_bodies, 6), dtype=torch.float64).pin_memory()
+    self.draws = torch.zeros((sampler.n_bodies, 6), dtype=torch.float64, device=self.dev)
+
+  def _energy(self):
+    s = self.s
+    with self.torch.cuda.device(self.dev):
+      self.ctx.set_positions(self.r_new, s.blob_radius, s.periodic_length, wall=False)
+      u_one, u_pair = self.ctx.blob_potential(s.repulsion_strength, s.debye_length, s.blob_radius,
+                                              repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
+                                              weight=s.weight, potential=s.potential)
+    return u_one + u_pair
+
+  def _propose(self, loc, quat, n_free, max_angle_shift):
+    with self.torch.cuda.device(self.dev):
+      self.ctx.mcmc_propose_device(self.blob_body, self.blob_ref, self.ref, loc, quat, self.draws, n_free, max_angle_shift,
+                                   self.loc_new, self.quat_new, self.r_new)
+
+  def current_energy(self):
+    self._propose(self.loc, self.quat, 0, 0.0)       # no free body: the current configuration's blob coordinates
+    return self._energy()
+
+  def upload(self, draws):
+    self.draws_host.numpy()[...] = draws
+    self.draws.copy_(self.draws_host, non_blocking=True)
+
+  def compose(self, max_angle_shift):
+    self._propose(self.loc, self.quat, self.s.n_free, max_angle_shift)
+
+  def propose(self, draws, max_angle_shift):
+    self.upload(draws)
+    self.compose(max_angle_shift)
+    return self._energy()
+
+  def accept(self):      # the proposed state becomes current: a swap of handles, no copy
+    self.loc, self.loc_new = self.loc_new, self.loc
+    self.quat, self.quat_new = self.quat_new, self.quat
+
+  def configuration(self):
+    return self.loc.cpu().numpy(), self.quat.cpu().numpy()
+
+  def close(self):
+    self.ctx.close()
+
+
+class MCMCSampler(object):
+  """many_body_MCMC.py:100-304.  `read`: a ReadInput (or the path of a deck).  After run(): energy_log (the start energy,
+  then every proposal's), accepted (one bool per step), accepted_moves, max_translation, max_angle_shift, and -- with
+  keep_saved (default: only when no files are written) -- saved: step -> (locations, quaternions) of every save."""
+
+  def __init__(self, read, device=0, potential="soft", rng="reference", energy=None, write_files=True, verbose=False,
+               check_user_potential=True, keep_saved=None):
+    if check_user_potential:
+      refuse_user_defined_potential(".")
+    if potential not in ("soft", "yukawa"):
+      raise ValueError("potential must be 'soft' or 'yukawa', got %r" % (potential,))
+    if rng not in ("reference", "batched"):
+      raise ValueError("rng must be 'reference' or 'batched', got %r" % (rng,))
+    self.read = read = ReadInput(read) if isinstance(read, str) else read
+    self.potential, self.rng_mode, self.write_files, self.verbose = potential, rng, write_files, verbose
+    if read.n_steps <= read.initial_step:
+      raise ValueError("n_steps (%d) must exceed initial_step (%d)" % (read.n_steps, read.initial_step))
+    if read.save_clones not in ("one_file_per_step", "one_file"):
+      raise ValueError("save_clones = %s is not implemented: use one_file_per_step or one_file" % read.save_clones)
+    self.blob_radius = float(read.blob_radius)
+    self.periodic_length = np.asarray(read.periodic_length, dtype=np.float64)
+    self.weight = 1.0 * read.g
+    self.kT = read.kT
+    self.repulsion_strength, self.debye_length = read.repulsion_strength, read.debye_length
+    self.repulsion_strength_wall, self.debye_length_wall = read.repulsion_strength_wall, read.debye_length_wall
+    # bodies, structure after structure (many_body_MCMC.py:107-125)
+    refs, locs, quats, blob_body, blob_ref = [], [], [], [], []
+    self.body_types, n_free, max_len, row0, body0 = [], 0, 0.0, 0, 0
+    for k, structure in enumerate(read.structures):
+      ref = read_vertex_file(read.resolve(structure[0]))[:, :3]
+      nb, loc, quat = read_clones_file(read.resolve(structure[1]))
+      self.body_types.append(nb)
+      if nb > 0:
+        max_len = max(max_len, body_length(ref, self.blob_radius))
+      if k < read.num_free_bodies:
+        n_free += nb
+      refs.append(ref); locs.append(loc); quats.append(quat)
+      blob_body.append(np.repeat(body0 + np.arange(nb), len(ref)))
+      blob_ref.append(np.tile(row0 + np.arange(len(ref)), nb))
+      row0 += len(ref); body0 += nb
+    self.ref_all = np.concatenate(refs) if refs else np.zeros((0, 3))
+    self.loc0 = np.concatenate(locs).reshape(-1, 3)
+    self.quat0 = np.concatenate(quats).reshape(-1, 4)
+    self.blob_body = np.concatenate(blob_body).astype(np.int64)
+    self.blob_ref = np.concatenate(blob_ref).astype(np.int64)
+    self.n_bodies, self.n_free, self.n_blobs = body0, n_free, self.blob_body.size
+    self.max_body_length = max_len
+    self.max_translation = self.blob_radius * 0.1
+    self.max_angle_shift = self.max_translation / self.max_body_length
+    self.accepted_moves, self.acceptance_ratio = 0, 0.5
+    self.energy_log, self.accepted, self.saved = [], [], {}
+    # saved configurations stay in memory only when asked for, or when no file receives them
+    self.keep_saved = (not write_files) if keep_saved is None else bool(keep_saved)
+    self.draw_seconds = 0.0
+    self.state = _HostState(self, energy) if energy is not None else _DeviceState(self, device)
+
+  def close(self):
+    self.state.close()
+
+  # ---- draws -------------------------------------------------------------------------------------------------------------
+  def _draws(self, rng):
+    d = np.zeros((self.n_bodies, 6))
+    t = self.max_translation
+    if self.rng_mode == "reference":
+      for k in range(self.n_free):          # the legacy generator caches a Gaussian: this order cannot be vectorised
+        d[k, 0:3] = rng.uniform(-t, t, 3)
+        d[k, 3:6] = rng.normal(0, 1, 3)
+    else:
+      d[:self.n_free, 0:3] = rng.uniform(-t, t, (self.n_free, 3))
+      d[:self.n_free, 3:6] = rng.normal(0, 1, (self.n_free, 3))
+    return d
+
+  # ---- output ------------------------------------------------------------------------------------------------------------
+  def _save(self, step):
+    loc, quat = self.state.configuration()
+    if self.keep_saved:
+      self.saved[step] = (np.array(loc), np.array(quat))
+    if not self.write_files:
+      return
+    read, offset = self.read, 0
+    for i, ID in enumerate(read.structures_ID):
+      if read.save_clones == "one_file_per_step":
+        name, status = read.output_name + "." + ID + "." + str(step).zfill(8) + ".clones", "w"
+      else:
+        name, status = read.output_name + "." + ID + ".config", ("w" if step == 0 else "a")
+      with open(name, status) as f:
+        f.write(str(self.body_types[i]) + "\n")
+        for j in range(self.body_types[i]):
+          x, q = loc[offset + j], quat[offset + j]
+          f.write("%s %s %s %s %s %s %s\n" % (float(x[0]), float(x[1]), float(x[2]), float(q[0]), float(q[1]), float(q[2]), float(q[3])))
+      offset += self.body_types[i]
+
+  def info_lines(self, last_step):
+    return ["acceptance ratio = " + str(self.accepted_moves / (last_step + 2.0 - self.read.initial_step)),
+            "accepted_moves = " + str(self.accepted_moves),
+            "final max_translation = " + str(self.max_translation),
+            "final max_angle_shift = " + str(self.max_angle_shift)]
+
+  # ---- the chain -----------------------------------------------------------------------------------------------------------
+  def run(self, rng=None):
+    read = self.read
+    if self.write_files:
+      shutil.copyfile(read.input_file, read.output_name + ".inputfile")
+    if rng is None:
+      rng = read.random_generator(save=self.write_files)
+    start = time.time()
+    current = np.float64(self.state.current_energy())
+    self.energy_log.append(float(current))
+    kT = np.float64(self.kT)
+    step = read.initial_step
+    for step in range(read.initial_step, read.n_steps):
+      t0 = time.perf_counter()
+      draws = self._draws(rng)
+      self.draw_seconds += time.perf_counter() - t0
+      sample = np.float64(self.state.propose(draws, self.max_angle_shift))
+      self.energy_log.append(float(sample))
+      with np.errstate(over="ignore", invalid="ignore"):        # numpy's comparison: a NaN or inf energy rejects
+        ok = bool(rng.uniform(0.0, 1.0) < np.exp(-(sample - current) / kT))
+      self.accepted.append(ok)
+      if ok:
+        current = sample
+        self.accepted_moves += 1
+        self.acceptance_ratio = self.acceptance_ratio * 0.95 + 0.05
+        self.state.accept()
+      else:
+        self.acceptance_ratio = self.acceptance_ratio * 0.95
+      # step size: +-2 % during the first half of the negative steps
+      if step < 0 and step < read.initial_step // 2:
+        self.max_translation = self.max_translation * (1.02 if self.acceptance_ratio > 0.5 else 0.98)
+        self.max_angle_shift = self.max_translation / self.max_body_length
+      if (step % read.n_save) == 0 and step >= 0:
+        if self.verbose:
+          print("MCMC, step = ", step, ", wallclock time = ", time.time() - start, ", acceptance ratio = ",
+                self.accepted_moves / (step + 1.0 - read.initial_step))
+        self._save(step)
+    if ((step + 1) % read.n_save) == 0 and step >= 0:         # the "final" save of the reference
+      self._save(step + 1)
+    self.last_step = step
+    if self.verbose:
+      print("\nacceptance ratio = ", self.accepted_moves / (step + 2.0 - read.initial_step))
+      print("accepted_moves = ", self.accepted_moves)
+      print("Total time = ", time.time() - start)
+    if self.write_files:
+      with open(read.output_name + ".time", "w") as f:
+        f.write(str(time.time() - start) + "\n")
+      with open(read.output_name + ".MCMC_info", "w") as f:
+        f.write("\n".join(self.info_lines(step)) + "\n")
+    return self
+
+
+def main(argv=None):
+  ap = argparse.ArgumentParser(prog="python -m rigidmultiblobswall_amd.mcmc", description=__doc__.split("\n\n")[0])
+  ap.add_argument("inputfile", nargs="?", default="data.main")
+  ap.add_argument("--device", type=int, default=0)
+  ap.add_argument("--potential", choices=("soft", "yukawa"), default="soft")
+  ap.add_argument("--rng", choices=("reference", "batched"), default="reference")
+  args = ap.parse_args(argv)
+  sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True)
+  try:
+    sampler.run()
+  finally:
+    sampler.close()
+  return 0
+
+
+if __name__ == "__main__":
+  sys.exit(main())

@@ -1,0 +1,67 @@
+"""Potential energy of a blob configuration -- the `many_body_potential_pycuda` surface on MI355X.
+
+Replaces many_bodyMCMC/many_body_potential_pycuda.py:234-351 (one CUDA thread per blob, allocation and both copies on
+every call) behind the same calls and keyword names:
+  blobs_potential_hip(r_vectors, periodic_length=L, debye_length_wall=.., repulsion_strength_wall=.., debye_length=..,
+                      repulsion_strength=.., weight=.., blob_radius=..) -> float
+  bodies_potential_hip(bodies, **kwargs) -> 0.0          (the reference's default body potentials are empty)
+  compute_total_energy_hip(bodies, r_vectors, **kwargs)  -> U_blobs + U_bodies
+`potential="soft"|"yukawa"` is the one extra keyword: the module's own form, or the Yukawa form of the reference's only
+MCMC example (examples/boomerang_suspension/potential_pycuda_user_defined.py).  A reference checkout binds it with
+  import rigidmultiblobswall_amd.potential as p; many_body_potential_pycuda.compute_total_energy = p.compute_total_energy_hip
+"""
+import numpy as np
+
+from .context import MobilityContext, POTENTIAL_FORMS
+
+_ctx = None
+
+
+def _context():
+  """Own context (raw positions, as forces.py) on the first device mobility.py is configured with."""
+  global _ctx
+  from . import mobility
+  dev = mobility.devices()[0]
+  if _ctx is None or _ctx.device != dev:
+    if _ctx is not None:
+      _ctx.close()
+    _ctx = MobilityContext(dev)
+  return _ctx
+
+
+def reset():
+  """Drop the module-level context (frees device memory)."""
+  global _ctx
+  if _ctx is not None:
+    _ctx.close()
+  _ctx = None
+
+
+def potential_terms(ctx, **kwargs):
+  """(U_one_blob, U_pair) of ctx's resident positions from the reference's keyword arguments."""
+  return ctx.blob_potential(kwargs.get('repulsion_strength'), kwargs.get('debye_length'), kwargs.get('blob_radius'),
+                            repulsion_strength_wall=kwargs.get('repulsion_strength_wall') or 0.0,
+                            debye_length_wall=kwargs.get('debye_length_wall') or 1.0, weight=kwargs.get('weight') or 0.0,
+                            potential=kwargs.get('potential', 'soft'))
+
+
+def blobs_potential_hip(r_vectors, *args, **kwargs):
+  L = kwargs.get('periodic_length')
+  if L is None:
+    L = np.zeros(3)
+  if kwargs.get('potential', 'soft') not in POTENTIAL_FORMS:
+    raise ValueError("potential must be 'soft' or 'yukawa'")
+  ctx = _context()
+  # wall=False: raw heights, the reference passes r_vectors untouched
+  ctx.set_positions(r_vectors, kwargs.get('blob_radius'), L, wall=False)
+  u_one, u_pair = potential_terms(ctx, **kwargs)
+  return u_one + u_pair
+
+
+def bodies_potential_hip(bodies, *args, **kwargs):
+  """one_body_potential / body_body_potential of the reference are empty (many_body_potential_pycuda.py:125-155)."""
+  return 0.0
+
+
+def compute_total_energy_hip(bodies, r_vectors, *args, **kwargs):
+  return blobs_potential_hip(r_vectors, *args, **kwargs) + bodies_potential_hip(bodies, *args, **kwargs)

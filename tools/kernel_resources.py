@@ -6,6 +6,7 @@ residency, so a change that moves an instance across a register or LDS boundary 
 
   python tools/kernel_resources.py                  this tree
   python tools/kernel_resources.py OTHER_TREE       OTHER_TREE | this tree, side by side, differing rows marked
+  python tools/kernel_resources.py --potential      potential_kernel next to sym_force_kernel, every pair loop of each
 """
 import os
 import re
@@ -43,7 +44,57 @@ def table(root):
   return rows
 
 
+def pair_loops(asm, mangled, floor=30):
+  """(header, VALU, fp64 VALU, LDS instructions) of EVERY inner loop of a kernel with at least `floor` VALU instructions:
+  a kernel with a plain and a guarded pair loop (potential_kernel) has two, isa_stats.kernel_loop_stats reports the larger."""
+  lines = asm.split("\n")
+  start = next(i for i, l in enumerate(lines) if l.startswith(mangled) and ":" in l)
+  end = start
+  while "s_endpgm" not in lines[end]:
+    end += 1
+  blocks, cur = [], None
+  for l in lines[start:end]:
+    m = re.match(r"^\.(LBB\d+_\d+):(.*)$", l)
+    if m:
+      cur = [m.group(1), m.group(2), []]
+      blocks.append(cur)
+    elif cur is not None and re.match(r"^\s+;", l):
+      cur[1] += " " + l.strip()
+    elif cur is not None:
+      m = re.match(r"^\s+([a-z_0-9]+)", l)
+      if m:
+        cur[2].append(m.group(1))
+  out = []
+  for label, ann, _ in blocks:
+    if "Inner Loop Header" not in ann:
+      continue
+    ops = [o for b in blocks if b[0] == label or re.search(r"in Loop: Header=%s\b" % label[1:], b[1]) for o in b[2]]
+    valu = [o for o in ops if o.startswith("v_")]
+    if len(valu) >= floor:
+      out.append((label, len(valu), sum("f64" in o for o in valu), sum(o.startswith("ds_") for o in ops)))
+  return out
+
+
+def potential_table(root):
+  """potential_kernel (rmb_potential.hip) next to sym_force_kernel (rmb_sym.hip): resources and every pair loop."""
+  for unit, pattern in (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel")):
+    asm = subprocess.run([isa_stats.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-S",
+                          "--cuda-device-only", "-o", "-", os.path.join(root, "rigidmultiblobswall_amd", "csrc", unit)],
+                         check=True, capture_output=True, text=True).stdout
+    for m in INFO.finditer(asm):
+      if pattern not in m.group(1):
+        continue
+      name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+      name = re.sub(r"\(.*", "", name).replace("void ", "")
+      code, sgpr, vgpr, scratch, lds = (int(g) for g in m.groups()[1:])
+      loops = "  ".join("loop %d VALU / %d fp64 / %d LDS" % l[1:] for l in pair_loops(asm, m.group(1)))
+      print("%-44s vgpr %3d sgpr %3d scratch %d lds %5d res %d code %4d  %s" % (name, vgpr, sgpr, scratch, lds, resident(vgpr, lds), code, loops))
+
+
 if __name__ == "__main__":
+  if "--potential" in sys.argv:
+    potential_table(isa_stats.ROOT)
+    sys.exit(0)
   here = table(isa_stats.ROOT)
   other = table(sys.argv[1]) if len(sys.argv) > 1 else None
   for name in sorted(here):
