@@ -163,7 +163,7 @@ template <bool PERIODIC, bool RADII> struct ForceOp {
       const double r = r2 * ir;
       // far: -(eps/b) exp(-(r-2a)/b)/r ; near (r <= 2a): -(eps/b)/max(r,1e-25) = -(eps/b) min(1/r, 1e25)
       const double two_a = RADII ? tg.ra + q1.y : a.two_a;
-      // branch-free (sym_kernels.h pair_force): x = 0 exactly for r <= 2a, exp(0) = 1, min(1/r, 1e25) = 1/r beyond
+      // branch-free (sym_force_kernels.h pair_force): x = 0 exactly for r <= 2a, exp(0) = 1, min(1/r, 1e25) = 1/r beyond
       const double e = exp_nonpositive(a.ec, fmin((two_a - r) * a.inv_b, 0.0));
       double f0 = -a.eps_over_b * (e * fmin(ir, 1e25));
       if (j0 + s == ti) f0 = 0.0;  // i == j (r2 = 0 -> ir = inf; select, do not multiply)

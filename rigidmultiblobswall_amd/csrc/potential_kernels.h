@@ -2,8 +2,8 @@
 //
 // U = sum_i u1(z_i) + sum_{i<j} u2(r_ij), the reference's many_bodyMCMC/many_body_potential_pycuda.py:64-119 (one thread
 // per blob, inner loop j > i over global memory).  Here every unordered pair is met once on the schedule of
-// sym_force_kernel (sym_kernels.h): a work unit is a tile pair I <= J, lane = blob of tile I, tile J staged in the wave's
-// LDS slab and read by rotation; the same unit_seek / unit_next, xcd_swizzle, strided chunks, tile bounds and exact-zero
+// sym_force_kernel (sym_force_kernels.h): a work unit is a tile pair I <= J, lane = blob of tile I, tile J staged in the wave's
+// LDS slab and read by rotation; the same unit_seek / unit_next, xcd_swizzle (sym_schedule.h), strided chunks, tile bounds and exact-zero
 // culling.  The result is a scalar, so there is nothing to transpose: every lane keeps two fp64 sums (one-blob, pair) for
 // the whole launch, a wave reduces its lanes with a fixed butterfly and stores ONE pair of partials, and
 // potential_finish_kernel adds the partials in a fixed order -- no atomic anywhere, bit-reproducible for a given launch
@@ -16,7 +16,8 @@
 //     Units whose two tiles lie above the wall (zmin > 0, wave-uniform from the tile bounds) skip the test.
 //   * minimal image in x and y only; distinct blobs at r = 0 give the finite contact value (soft) / inf (yukawa).
 #pragma once
-#include "sym_kernels.h"
+#include "pair_ops.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 

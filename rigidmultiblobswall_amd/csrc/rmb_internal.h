@@ -4,10 +4,10 @@
 //   rmb_context.hip  error state, context life cycle, streams, options, timing ring, diagnostics, default context
 //   rmb_plan.hip     launch plans: source chunks, residency, the balanced step schedule of the symmetric kernels,
 //                    pair-shard ranges, kernel-uniform constants
-//   rmb_sym.hip      launchers of the symmetric (each unordered pair once) fp64 kernels: sym / sym2 / symx / symx_det,
-//                    the symmetric force kernel
-//   rmb_sym32.hip    their single-precision twins (handed over as launch thunks)
-//   rmb_symx_coop.hip  workgroup-cooperative instances of the generic symmetric skeleton (launch thunks too)
+//   rmb_sym.hip      the symmetric (each unordered pair once) fp64 sweeps: one launch path (fill_sym_args, choose_sym,
+//                    sym_launch below) under sym / sym2 / symx / the symmetric force kernel; symx_det
+//   rmb_sym32.hip    their single-precision twins (handed over as SymKernel thunks)
+//   rmb_symx_coop.hip  workgroup-cooperative instances of the generic symmetric skeleton (SymKernel thunks too)
 //   rmb_symx2t.hip, rmb_symx2t_per.hip  two-targets-per-lane instances of the generic skeleton, open / pseudo-periodic
 //   rmb_sort.hip     Morton ordering of the blobs for the force kernel's tile culling (rocPRIM radix sort)
 //   rmb_sweep.hip    the one-sided kernels (one frame, onesided_kernels.h; one launcher, one_sided_launch below): sweep,
@@ -26,8 +26,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pair_ops.h"
@@ -118,7 +120,8 @@ struct rmb_ctx {
   long opt_fused_symmetric = 1;  // tt+tr: 1 = single symmetric pass (symx_kernels.h), 2 = two symmetric passes, 0 = one-sided fused sweep
   long opt_symx_single = 0;      // route tt / tr / rt / rr through the generic skeleton (A/B against sym_kernel)
   long opt_deterministic = 0;  // force the atomic-free sweep kernel everywhere
-  int last_path = 0;           // 0 = sweep, 1 = symmetric (per wave), 2 = deterministic symmetric, 3 = symmetric, workgroup-cooperative
+  int last_path = 0;           // 0 = sweep, 1 = symmetric (per wave), 2 = deterministic symmetric, 3 = symmetric, workgroup-cooperative,
+                               // 4 = symmetric, two target blobs per lane
   long opt_sym_wps = 0;        // cap on resident workgroups per CU for the symmetric kernel (0 = occupancy limit)
   long opt_sym_pin = 1;        // pad dynamic LDS so residency is exactly that number
   long opt_precision = 64;     // 32: M_tt f (open boundaries) in single precision (sym32_kernels.h); everything else fp64
@@ -223,6 +226,33 @@ int one_sided_launch(rmb_ctx* c, Args a) {
 struct SymPlan { long blocks; long steps_per_wave; size_t dyn_lds; bool sub_round; long round; };   // round: resident workgroups; sub_round: less work than that
 int plan_sym(rmb_ctx* c, const void* fn, int* occ_cache, size_t static_lds, long total, bool pin, SymPlan* out,
              int declared_waves = 0, long fine_auto = 0);
+// A symmetric sweep kernel as the launch path sees it: every instance, in whichever translation unit it is compiled
+// (fp64 and fp32, per wave, workgroup-cooperative, two targets per lane, forces, potential), is handed over in this shape.
+struct SymKernel {
+  const void* fn = nullptr;   // host handle of the kernel (occupancy / attributes); nullptr = the operation has no such instance
+  size_t static_lds = 0;
+  int* occ = nullptr;         // cache of resident_blocks(fn)
+  int waves_per_eu = 0;       // the amdgpu_waves_per_eu bound plan_sym caps the residency with (its `declared_waves`), 0 = none
+  // `args` points to the argument struct of the fp64 kernel (rmb::SymArgs / Sym2Args / SymXArgs / SymForceArgs /
+  // PotentialArgs); the fp32 twins convert the kernel-uniform constants `k` to float, the others ignore them
+  void (*launch)(const void* args, const rmb::PairConsts& k, unsigned blocks, size_t dyn_lds, hipStream_t s) = nullptr;
+  explicit operator bool() const { return fn != nullptr; }
+};
+template <class Args, void (*KERNEL)(Args)>
+void sym_kernel_launch(const void* args, const rmb::PairConsts&, unsigned blocks, size_t dyn_lds, hipStream_t s) {
+  hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(64 * rmb::kSymWaves), dyn_lds, s, *static_cast<const Args*>(args));
+}
+// the thunk of a kernel that takes its argument struct and nothing else (one occupancy cache per kernel)
+template <class Args, void (*KERNEL)(Args)>
+SymKernel sym_kernel_of(size_t static_lds, int waves_per_eu = 0) {
+  static int occ = 0;
+  return SymKernel{(const void*)KERNEL, static_lds, &occ, waves_per_eu, sym_kernel_launch<Args, KERNEL>};
+}
+// The non-pinned plan of the culling sweeps (blob-blob forces, potential energy): "sym_oversub" resident rounds capped
+// by one workgroup per 256 steps, and a quarter of "sym_chunk_steps" per strided chunk -- the surviving units are few
+// and uneven, shorter chunks balance them (3D cloud of 1e5 blobs 3.36 -> 3.05 ms, monolayer unchanged;
+// tools/experiments/exp_force_ab.py).  *chunk_steps = 0: one contiguous range per wave.
+void plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps);
 void shard_ranges(long n, long n_units, long shard, long nshards, long* step_begin, long* step_end, long* self_begin,
                   long* self_end);
 int sym_accumulators(rmb_ctx* c, long n_pad);
@@ -231,12 +261,82 @@ int sym_accumulators(rmb_ctx* c, long n_pad);
 long chunked_steps(const rmb_ctx* c, long total, long n_sched, long spw, long target);
 // whether the symmetric (each unordered pair once) path applies to the resident configuration
 bool sym_applies(const rmb_ctx* c);
+inline double inv_length(double L) { return L > 0 ? 1.0 / L : 0.0; }   // reciprocal of a pseudo-periodic length (<= 0: open)
 
 // ---- rmb_sym.hip -------------------------------------------------------------------------------------------
 // SX_K2 + 4 (k - 2) + kind: one block on k = 2..4 vectors
 enum SymXOp { SX_TT = 0, SX_TR, SX_RT, SX_RR, SX_FUSED, SX_GRAND, SX_COLF, SX_FREE, SX_RADII, SX_K2, SX_COUNT = SX_K2 + 12 };
 // Configuration a symmetric pass runs on: the context's resident one, or a caller-packed one (per-blob radii)
 struct SymConf { const double4* pos; long n; double L[3]; int wall; const double* extra; };
+template <class A, class = void> struct HasNPad : std::false_type {};
+template <class A> struct HasNPad<A, std::void_t<decltype(A::n_pad)>> : std::true_type {};
+template <class A, class = void> struct HasPrefactor : std::false_type {};
+template <class A> struct HasPrefactor<A, std::void_t<decltype(A::prefactor)>> : std::true_type {};
+// Fills the fields the argument structs of the symmetric sweeps share by name: configuration, tile count, unit order,
+// box, and on the unit grid of the chosen kernel (`n_units`) the step range of pair shard `shard` of `nshards`; with
+// global accumulators (every struct but the potential's) also n_pad / n_units / the z period; for the mobility sweeps
+// (the structs with a prefactor) the self-term ownership and the kernel-uniform constants.  Call after sym_accumulators.
+template <class Args>
+void fill_sym_args(Args& a, const SymConf& cf, const rmb_ctx* c, double eta, long n_units, long shard, long nshards) {
+  const long tiles = (cf.n + 63) / 64;
+  long step_begin, step_end, self_begin, self_end;
+  shard_ranges(cf.n, n_units, shard, nshards, &step_begin, &step_end, &self_begin, &self_end);
+  a.pos = cf.pos;
+  a.n = cf.n; a.n_tiles = (int)tiles;
+  a.order = (int)c->opt_sym_order; a.xcd = (int)c->opt_sym_xcd;
+  a.step_end = step_end;
+  a.Lx = cf.L[0]; a.Ly = cf.L[1];
+  a.iLx = inv_length(cf.L[0]); a.iLy = inv_length(cf.L[1]);
+  if constexpr (HasNPad<Args>::value) {
+    a.acc = (double*)c->symbuf.p;
+    a.n_pad = 64 * tiles; a.n_units = n_units;
+    a.step_begin = step_begin;
+    a.Lz = cf.L[2]; a.iLz = inv_length(cf.L[2]);
+  }
+  if constexpr (HasPrefactor<Args>::value) {
+    a.self_begin = self_begin; a.self_end = self_end;
+    a.prefactor = 1.0 / (8.0 * M_PI * eta);
+    a.k = make_pair_consts(c->a > 0.0 ? c->a : 1.0);   // unused by the per-blob-radii operation
+  }
+}
+// The launch of every symmetric sweep: bookkeeping of the last launch (`path` = the last_path code), the wave_clock
+// buffer when the argument struct has one (`wave_clock` points at its field), the sweep between the timing events,
+// then the finishing kernel `fin` on `fin_blocks` workgroups of 256 (nullptr: the caller finishes the sums itself).
+template <class Args>
+int sym_launch(rmb_ctx* c, const SymKernel& k, int path, long blocks, size_t dyn_lds, Args& a, const rmb::PairConsts& pk,
+               void (*fin)(Args), long fin_blocks, long long** wave_clock = nullptr) {
+  c->last_path = path; c->last_tiles = a.n_tiles; c->last_chunks = 0; c->last_wgs = blocks;
+  if (wave_clock) {
+    *wave_clock = nullptr;
+    if (c->opt_wave_clock) {
+      // [waves][2] stamps (start, end | placement); sym2t_kernel adds a second region [waves][2] of per-wave phase totals in
+      // shader-clock cycles (staging incl. its wait, everything) -- rmb_wave_clock_collect hands out both as 2 x waves rows
+      c->wave_clock_n = blocks * rmb::kSymWaves * (path == 4 ? 2 : 1);
+      if (int rc = c->wave_clock.reserve((size_t)2 * c->wave_clock_n * sizeof(long long))) return rc;
+      *wave_clock = (long long*)c->wave_clock.p;
+    }
+  }
+  int slot;
+  if (int rc = timing_begin(c, &slot)) return rc;
+  k.launch(&a, pk, (unsigned)blocks, dyn_lds, c->stream);
+  RMB_HIP(hipGetLastError());
+  if (int rc = timing_end(c, slot)) return rc;
+  if (!fin) return 0;
+  hipLaunchKernelGGL(fin, dim3((unsigned)fin_blocks), dim3(256), 0, c->stream, a);
+  RMB_HIP(hipGetLastError());
+  return 0;
+}
+// Tile bounds of the culling sweeps (forces, potential): the Morton-sorted copy (rmb_sort.hip; `keep_perm`: along the
+// permutation that is already there) or the bounds of the caller's order; use_tile_bounds points the arguments at them.
+int build_tile_bounds(rmb_ctx* c, bool sorted, bool keep_perm);
+template <class Args>
+void use_tile_bounds(const rmb_ctx* c, Args& a) {
+  if (c->force_sorted) {
+    a.pos = (const double4*)c->fpos.p;
+    a.perm = (const unsigned*)c->fperm.p;
+  }
+  a.bounds = (const double*)c->tile_bounds.p;
+}
 // no_finalize: leave the raw sums in the accumulators (c->symbuf: [3][n_pad], unscaled, no self term) -- the caller
 // launches its own finishing kernel (rmb_rigid_operator_device); not for the pseudo-periodic / fp32 routes
 int sym_device(rmb_ctx* c, int kind, const double* v, double eta, double* out, long shard = 0, long nshards = 1,
@@ -254,25 +354,14 @@ int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, doubl
 int force_sort_positions(rmb_ctx* c);
 int force_regather_positions(rmb_ctx* c);   // sorted copy + tile bounds with the permutation already there
 
-// ---- rmb_sym32.hip: single-precision twins as launch thunks ---------------------------------------------------
-// fn = host handle of the kernel (occupancy / attributes), nullptr when the operation has no fp32 twin;
-// launch() converts the kernel-uniform constants to float and enqueues; `args` points to the fp64 kernel's argument
-// struct (rmb::SymArgs / rmb::SymXArgs / rmb::SymForceArgs).
-struct Kernel32 {
-  const void* fn;
-  size_t static_lds;
-  int* occ;
-  void (*launch)(const void* args, const rmb::PairConsts& k, unsigned blocks, size_t dyn_lds, hipStream_t s);
-};
-Kernel32 sym32_tt(bool wall);
-Kernel32 symx32(int sx, bool wall);
-Kernel32 sym_force32(bool radii);
-// ---- rmb_symx_coop.hip: workgroup-cooperative instances of the generic skeleton, same thunk shape (fp64) ---------
-Kernel32 symx_coop(int sx, bool wall, bool periodic);
-// ---- rmb_symx2t.hip / rmb_symx2t_per.hip: two-targets-per-lane instances of the generic skeleton (symx2t_kernels.h) ------
-// fn == nullptr when the operation has none; *waves_per_eu = what the instance was compiled for (plan_sym's residency cap)
-Kernel32 symx_two_open(int sx, bool wall, int* waves_per_eu);
-Kernel32 symx_two_periodic(int sx, bool wall, int* waves_per_eu);
+// ---- rmb_sym32.hip / rmb_symx_coop.hip / rmb_symx2t*.hip: instances compiled in translation units of their own --------
+// nullptr handle when the operation has no such instance
+SymKernel sym32_tt(bool wall);
+SymKernel symx32(int sx, bool wall);
+SymKernel sym_force32(bool radii);
+SymKernel symx_coop(int sx, bool wall, bool periodic);
+SymKernel symx_two_open(int sx, bool wall);
+SymKernel symx_two_periodic(int sx, bool wall);
 
 // ---- rmb_sweep.hip -----------------------------------------------------------------------------------------
 int pack_positions(rmb_ctx* c, const double* r_dev, long n, double a, const double* L, int wall);

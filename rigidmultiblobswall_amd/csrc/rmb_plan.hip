@@ -107,7 +107,7 @@ int sym_accumulators(rmb_ctx* c, long n_pad) {
 }
 
 
-// Static, exactly balanced schedule (sym_kernels.h): whole multiples of the resident workgroup count so that every
+// Static, exactly balanced schedule (sym_kernels.h, sym_schedule.h): whole multiples of the resident workgroup count so that every
 // SIMD gets the same number of steps.  `pin` pads dynamic LDS so that exactly `wps` workgroups fit a CU (equal steps
 // per wave is then equal work per SIMD); CU count and LDS size come from hipDeviceProp_t (rmb_ctx_create).
 // `declared_waves`: the kernel's amdgpu_waves_per_eu bound (0 = none).  The occupancy API prices a kernel by its
@@ -176,6 +176,18 @@ long chunked_steps(const rmb_ctx* c, long total, long n_sched, long spw, long ta
   const long rounds = (spw + target / 2) / target;       // chunks per schedule unit
   if (rounds < 2) return spw;
   return (total + n_sched * rounds - 1) / (n_sched * rounds);
+}
+
+void plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps) {
+  long b = c->n_cu * resident_blocks(k.fn, k.occ) * c->opt_sym_oversub;
+  const long need = (total_steps + 255) / 256;
+  if (b > need) b = need;
+  if (b < 1) b = 1;
+  const long waves = b * rmb::kSymWaves;
+  const long spw = (total_steps + waves - 1) / waves;
+  const long ch = chunked_steps(c, total_steps, waves, spw, c->opt_sym_chunk_steps / 4);
+  *blocks = b;
+  *chunk_steps = ch < spw ? ch : 0;
 }
 
 // whether the symmetric (each unordered pair once) path applies to the resident configuration

@@ -10,8 +10,6 @@
 namespace rmbi {
 namespace {
 
-typedef void (*potential_fn)(const rmb::PotentialArgs);
-
 // The sweep + the finishing launch on the context's stream; the two sums end up in out_dev[0..1].
 int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
                           double* out_dev) {
@@ -27,14 +25,12 @@ int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, dou
   if (n == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, 2 * sizeof(double), c->stream)); return 0; }
   if (n > 0xffffffffL) return fail(RMB_ERR_ARG, "potential: more than 2^32 blobs");
 
-  rmb::PotentialArgs a;
-  a.pos = (const double4*)c->pos.p;
+  typedef rmb::PotentialArgs A;
+  A a;
+  // x and y only: the struct has no z period, the reference ignores periodic_length[2]
+  fill_sym_args(a, SymConf{(const double4*)c->pos.p, n, {c->L[0], c->L[1], c->L[2]}, 0, nullptr}, c, 0.0, tiles * (tiles + 1) / 2, 0, 1);
   a.perm = nullptr;
-  a.n = n; a.n_tiles = (int)tiles;
   a.order = 0; a.xcd = 0;      // as the force sweep (rmb_sym.hip): after culling the surviving units hug the diagonal
-  a.step_end = tiles * (tiles + 1) / 2 * 64;
-  a.Lx = c->L[0]; a.Ly = c->L[1];                 // x and y only: the reference ignores periodic_length[2]
-  a.iLx = a.Lx > 0 ? 1.0 / a.Lx : 0.0; a.iLy = a.Ly > 0 ? 1.0 / a.Ly : 0.0;
   const bool periodic = a.Lx > 0 || a.Ly > 0;
   a.eps = eps; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
   a.eps_wall = eps_wall; a.inv_b_wall = eps_wall != 0.0 ? 1.0 / b_wall : 0.0; a.a = blob_radius; a.weight = weight;
@@ -44,60 +40,30 @@ int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, dou
   // order); the Morton permutation is kept and rebuilt on every "potential_resort"-th evaluation.
   const bool sorted = c->opt_force_sort && tiles >= 32;
   bool rebuild = true;
-  if (sorted) {
-    rebuild = c->fperm_n != n || c->pot_sort_age < 0 || c->pot_sort_age + 1 >= c->opt_potential_resort;
-    if (rebuild) {
-      if (int rc = force_sort_positions(c)) return rc;
-      c->pot_sort_age = 0;
-    } else {
-      if (int rc = force_regather_positions(c)) return rc;
-      ++c->pot_sort_age;
-    }
-    a.pos = (const double4*)c->fpos.p;
-    a.perm = (const unsigned*)c->fperm.p;
-  } else {
-    if (int rc = c->tile_bounds.reserve((size_t)6 * tiles * sizeof(double))) return rc;
-    hipLaunchKernelGGL(rmb::tile_bounds_kernel, dim3((unsigned)tiles), dim3(64), 0, c->stream, (const double4*)c->pos.p, n,
-                       (double*)c->tile_bounds.p);
-    RMB_HIP(hipGetLastError());
-  }
+  if (sorted) rebuild = c->fperm_n != n || c->pot_sort_age < 0 || c->pot_sort_age + 1 >= c->opt_potential_resort;
+  if (int rc = build_tile_bounds(c, sorted, !rebuild)) return rc;
+  if (sorted) c->pot_sort_age = rebuild ? 0 : c->pot_sort_age + 1;
   // What the force path finds (rmb_sym.hip): after a full sort, or bounds in the caller's order, exactly what it would have
   // built itself for this configuration -- it may use them; a sorted copy along a REUSED permutation is correct too, but
   // not the order the forces alone would sum in, so the force path is told to build its own.
   c->tile_bounds_valid = rebuild;
   c->force_sorted = sorted;
-  a.bounds = (const double*)c->tile_bounds.p;
+  use_tile_bounds(c, a);
   const double reach = form == rmb::POT_SOFT ? 2.0 * blob_radius + 750.0 * b : 750.0 * b;
   a.cull2 = c->opt_force_cull ? reach * reach : std::numeric_limits<double>::infinity();
 
-  static int occ[2][2] = {{0, 0}, {0, 0}};
-  const potential_fn fn = form == rmb::POT_SOFT
-                              ? (periodic ? (potential_fn)rmb::potential_kernel<rmb::POT_SOFT, true> : (potential_fn)rmb::potential_kernel<rmb::POT_SOFT, false>)
-                              : (periodic ? (potential_fn)rmb::potential_kernel<rmb::POT_YUKAWA, true>
-                                          : (potential_fn)rmb::potential_kernel<rmb::POT_YUKAWA, false>);
-  long blocks = c->n_cu * resident_blocks((const void*)fn, &occ[form][periodic ? 1 : 0]) * c->opt_sym_oversub;
-  const long need = (a.step_end + 255) / 256;
-  if (blocks > need) blocks = need;
-  if (blocks < 1) blocks = 1;
+  const SymKernel k = form == rmb::POT_SOFT
+                          ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, true>>(0) : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, false>>(0))
+                          : (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true>>(0)
+                                      : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false>>(0));
+  long blocks;
+  plan_cull_sweep(c, k, a.step_end, &blocks, &a.chunk_steps);
   const long waves = blocks * rmb::kSymWaves;
-  {
-    const long spw = (a.step_end + waves - 1) / waves;
-    const long ch = chunked_steps(c, a.step_end, waves, spw, c->opt_sym_chunk_steps / 4);
-    a.chunk_steps = ch < spw ? ch : 0;
-  }
   if (int rc = c->pot_ws.reserve((size_t)(2 * waves + 2) * sizeof(double))) return rc;
   a.partial = (double*)c->pot_ws.p;
   a.n_partial = waves;
   a.out = out_dev;
-  c->last_path = 1; c->last_tiles = tiles; c->last_chunks = 0; c->last_wgs = blocks;
-  int slot;
-  if (int rc = timing_begin(c, &slot)) return rc;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64 * rmb::kSymWaves), 0, c->stream, a);
-  RMB_HIP(hipGetLastError());
-  if (int rc = timing_end(c, slot)) return rc;       // the sweep alone, as the force path brackets its own
-  hipLaunchKernelGGL(rmb::potential_finish_kernel, dim3(1), dim3(256), 0, c->stream, a);
-  RMB_HIP(hipGetLastError());
-  return 0;
+  return sym_launch(c, k, 1, blocks, 0, a, rmb::PairConsts{}, rmb::potential_finish_kernel, 1);
 }
 
 struct ProposeArgs {

@@ -1,7 +1,7 @@
 // rmb_sort.hip -- spatial ordering of the blobs for the force kernel's tile culling.
 //
 // sym_force_kernel skips a tile pair whose bounding boxes are further apart than the range of the exponential
-// (sym_kernels.h: tile_gap2).  How much that skips depends on how compact a 64-blob tile is in space, i.e. on the ORDER
+// (sym_schedule.h: tile_gap2).  How much that skips depends on how compact a 64-blob tile is in space, i.e. on the ORDER
 // in which the caller lists the blobs: a monolayer listed in lattice order loses 99 % of its tile pairs, the same
 // monolayer listed in random order none (profiles/r3_force_tile_culling.txt).  The reference's answer to the short
 // range of the force is a k-d tree (multi_bodies/forces_numba.py:141-271, `tree_numba`); here the blobs are sorted once
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void global_bounds_kernel(const double* tile_b
     for (int d = 0; d < 3; ++d) { box[d] = lo[d][0]; box[3 + d] = hi[d][0]; }
 }
 
-// bounding box of every 64-blob tile (same layout as rmb::tile_bounds_kernel, which lives with the force kernel)
+// bounding box of every 64-blob tile (same layout as rmb::tile_bounds_kernel of sym_schedule.h)
 __global__ __launch_bounds__(64) void tile_box_kernel(const double4* pos, long n, double* bounds) {
   const long T = blockIdx.x;
   const long i = 64 * T + threadIdx.x;

@@ -34,7 +34,7 @@ const sweep_launch_fn g_sweeps[rmb::KIND_COUNT][2][2] = {
 template <class Args>
 bool set_box(Args& a, const double* L) {
   a.Lx = L ? L[0] : 0.0; a.Ly = L ? L[1] : 0.0; a.Lz = L ? L[2] : 0.0;
-  a.iLx = a.Lx > 0 ? 1.0 / a.Lx : 0.0; a.iLy = a.Ly > 0 ? 1.0 / a.Ly : 0.0; a.iLz = a.Lz > 0 ? 1.0 / a.Lz : 0.0;
+  a.iLx = inv_length(a.Lx); a.iLy = inv_length(a.Ly); a.iLz = inv_length(a.Lz);
   return a.Lx > 0 || a.Ly > 0 || a.Lz > 0;
 }
 }  // namespace

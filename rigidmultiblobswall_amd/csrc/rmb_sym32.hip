@@ -1,6 +1,6 @@
 // rmb_sym32.hip -- the single-precision twins of the symmetric kernels (the reference's `precision = 'single'` build,
-// mobility/mobility_pycuda.py:7-19; sym32_kernels.h, symx32_kernels.h), handed to the fp64 launchers of rmb_sym.hip as
-// launch thunks so that this translation unit compiles on its own.
+// mobility/mobility_pycuda.py:7-19; sym32_kernels.h, symx32_kernels.h), handed to the launch path of rmb_sym.hip as
+// SymKernel thunks so that this translation unit compiles on its own.
 #include "rmb_internal.h"
 
 #include "sym32_kernels.h"
@@ -31,36 +31,28 @@ void launch_symx32(const void* args, const rmb::PairConsts& k, unsigned blocks, 
                      *static_cast<const rmb::SymXArgs*>(args), pair_consts32(k));
 }
 
-template <bool RADII>
-void launch_force32(const void* args, const rmb::PairConsts&, unsigned blocks, size_t dyn_lds, hipStream_t s) {
-  hipLaunchKernelGGL((rmb::sym_force32_kernel<RADII>), dim3(blocks), dim3(64 * rmb::kSymWaves), dyn_lds, s,
-                     *static_cast<const rmb::SymForceArgs*>(args));
-}
-
 template <class OP32>
-Kernel32 symx32_of(bool wall) {
+SymKernel symx32_of(bool wall) {
   static int occ[2] = {0, 0};
-  if (wall) return Kernel32{(const void*)rmb::symx32_kernel<OP32, true>, rmb::SymX32Lds<OP32>::bytes, &occ[1], launch_symx32<OP32, true>};
-  return Kernel32{(const void*)rmb::symx32_kernel<OP32, false>, rmb::SymX32Lds<OP32>::bytes, &occ[0], launch_symx32<OP32, false>};
+  if (wall) return SymKernel{(const void*)rmb::symx32_kernel<OP32, true>, rmb::SymX32Lds<OP32>::bytes, &occ[1], 0, launch_symx32<OP32, true>};
+  return SymKernel{(const void*)rmb::symx32_kernel<OP32, false>, rmb::SymX32Lds<OP32>::bytes, &occ[0], 0, launch_symx32<OP32, false>};
 }
 
 }  // namespace
 
-Kernel32 sym32_tt(bool wall) {
+SymKernel sym32_tt(bool wall) {
   static int occ[2] = {0, 0};
   const size_t lds = (sizeof(float) * 9 + sizeof(double) * 3) * rmb::kSymWaves * 64;
-  if (wall) return Kernel32{(const void*)rmb::sym32_tt_kernel<true>, lds, &occ[1], launch_sym32_tt<true>};
-  return Kernel32{(const void*)rmb::sym32_tt_kernel<false>, lds, &occ[0], launch_sym32_tt<false>};
+  if (wall) return SymKernel{(const void*)rmb::sym32_tt_kernel<true>, lds, &occ[1], 0, launch_sym32_tt<true>};
+  return SymKernel{(const void*)rmb::sym32_tt_kernel<false>, lds, &occ[0], 0, launch_sym32_tt<false>};
 }
 
-Kernel32 sym_force32(bool radii) {
-  static int occ[2] = {0, 0};
-  if (radii) return Kernel32{(const void*)rmb::sym_force32_kernel<true>, 0, &occ[1], launch_force32<true>};
-  return Kernel32{(const void*)rmb::sym_force32_kernel<false>, 0, &occ[0], launch_force32<false>};
+SymKernel sym_force32(bool radii) {     // no kernel-uniform mobility constants: the plain thunk
+  return radii ? sym_kernel_of<rmb::SymForceArgs, rmb::sym_force32_kernel<true>>(0) : sym_kernel_of<rmb::SymForceArgs, rmb::sym_force32_kernel<false>>(0);
 }
 
 // open boundaries only; the free-surface operation takes raw heights, so its wall = 0 instance serves both columns
-Kernel32 symx32(int sx, bool wall) {
+SymKernel symx32(int sx, bool wall) {
   switch (sx) {
     case SX_TT: return symx32_of<rmb::OpSingle32<rmb::KIND_TT>>(wall);
     case SX_TR: return symx32_of<rmb::OpSingle32<rmb::KIND_TR>>(wall);
@@ -81,7 +73,7 @@ Kernel32 symx32(int sx, bool wall) {
 #undef RMB_K32_ROW
 #undef RMB_K32
   }
-  return Kernel32{nullptr, 0, nullptr, nullptr};
+  return SymKernel{};
 }
 
 }  // namespace rmbi

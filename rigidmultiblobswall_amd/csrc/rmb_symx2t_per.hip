@@ -3,5 +3,5 @@
 #include "symx2t_instances.h"
 
 namespace rmbi {
-Kernel32 symx_two_periodic(int sx, bool wall, int* waves_per_eu) { return symx2t_detail::table<true>(sx, wall, waves_per_eu); }
+SymKernel symx_two_periodic(int sx, bool wall) { return symx2t_detail::table<true>(sx, wall); }
 }  // namespace rmbi

@@ -1,5 +1,5 @@
 // rmb_symx_coop.hip -- the workgroup-cooperative instances of the generic symmetric skeleton (symx_coop_kernels.h), in
-// a translation unit of their own (they compile in parallel with rmb_sym.hip) and handed to symx_device as launch thunks.
+// a translation unit of their own (they compile in parallel with rmb_sym.hip) and handed to symx_device as SymKernel thunks.
 #include "rmb_internal.h"
 
 #include "symx_coop_kernels.h"
@@ -9,27 +9,17 @@ namespace rmbi {
 namespace {
 
 template <class OP, bool WALL, bool PER>
-void launch_coop(const void* args, const rmb::PairConsts&, unsigned blocks, size_t dyn_lds, hipStream_t s) {
-  hipLaunchKernelGGL((rmb::symx_coop_kernel<OP, WALL, PER>), dim3(blocks), dim3(64 * rmb::kSymWaves), dyn_lds, s,
-                     *static_cast<const rmb::SymXArgs*>(args));
-}
-
-template <class OP, bool WALL, bool PER>
-Kernel32 one() {
-  static int occ = 0;
-  return Kernel32{(const void*)rmb::symx_coop_kernel<OP, WALL, PER>, rmb::SymXCoopLds<OP>::bytes, &occ, launch_coop<OP, WALL, PER>};
-}
+SymKernel one() { return sym_kernel_of<rmb::SymXArgs, rmb::symx_coop_kernel<OP, WALL, PER>>(rmb::SymXCoopLds<OP>::bytes); }
 
 template <class OP>
-Kernel32 of(bool wall, bool periodic) {
+SymKernel of(bool wall, bool periodic) {
   if (wall) return periodic ? one<OP, true, true>() : one<OP, true, false>();
   return periodic ? one<OP, false, true>() : one<OP, false, false>();
 }
 
 }  // namespace
 
-// (the struct is shared with the fp32 thunks: fn / static LDS / occupancy cache / launch)
-Kernel32 symx_coop(int sx, bool wall, bool periodic) {
+SymKernel symx_coop(int sx, bool wall, bool periodic) {
   switch (sx) {
     case SX_TT: return of<rmb::OpSingle<rmb::KIND_TT>>(wall, periodic);
     case SX_TR: return of<rmb::OpSingle<rmb::KIND_TR>>(wall, periodic);
@@ -50,7 +40,7 @@ Kernel32 symx_coop(int sx, bool wall, bool periodic) {
 #undef RMB_KC_ROW
 #undef RMB_KC
   }
-  return Kernel32{nullptr, 0, nullptr, nullptr};
+  return SymKernel{};
 }
 
 }  // namespace rmbi

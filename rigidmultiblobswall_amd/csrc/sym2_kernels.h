@@ -12,6 +12,7 @@
 // ds_read_b128), accumulators [2][3][n_pad].
 #pragma once
 #include "sym_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 

@@ -15,86 +15,9 @@
 // (2p + 1, 2p + 1) diagonal -- run row by row through the one-target loops of sym_kernel.
 #pragma once
 #include "sym_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
-
-// ---- unit order ------------------------------------------------------------------------------------------------
-// units of the row-pair grid: sum over pairs p of (T - 2p)
-__host__ __device__ inline long units2_before_pair(long p, long T) { return p * T - p * (p - 1); }
-__host__ __device__ inline long units2_total(long T) { return units2_before_pair((T + 1) / 2, T); }
-
-// order 0: pair by pair, J ascending.  order 1: the blocked order of sym_kernels.h on this grid -- super-blocks of
-// 16 row pairs (32 tile rows) x 32 tile columns, walked super-row by super-row, pair by pair inside a super-block (the
-// diagonal super-block is the staircase J >= 2p), so that waves which run at the same time share tiles in L2.
-constexpr int kOrd2Pairs = 1 << (kOrdShift - 1);     // row pairs per super-block
-
-// units before super-row B (all earlier super-rows are full): 16 B (T + 1 - 16 B)
-__host__ __device__ inline long blk2_units_before_row(long B, long T) { return (long)kOrd2Pairs * B * (T + 1 - (long)kOrd2Pairs * B); }
-
-__device__ __forceinline__ void unit2_seek(int order, long u, int T, int& p, int& J) {
-  const double b = (double)T + 1.0;
-  double disc = b * b - 4.0 * (double)u;
-  if (disc < 0.0) disc = 0.0;
-  const double y = (b - sqrt(disc)) * 0.5;             // smaller root of y (T + 1 - y) = u
-  if (order == 0) {
-    long q = (long)y;
-    const long P = ((long)T + 1) / 2;
-    if (q < 0) q = 0;
-    if (q > P - 1) q = P - 1;
-    while (q > 0 && units2_before_pair(q, T) > u) --q;
-    while (q + 1 < P && units2_before_pair(q + 1, T) <= u) ++q;
-    p = (int)q;
-    J = (int)(2 * q + (u - units2_before_pair(q, T)));
-    return;
-  }
-  const long NB = ((long)T + (1 << kOrdShift) - 1) >> kOrdShift;     // super-rows
-  long B = (long)(y / kOrd2Pairs);
-  if (B < 0) B = 0;
-  if (B > NB - 1) B = NB - 1;
-  while (B > 0 && blk2_units_before_row(B, T) > u) --B;
-  while (B + 1 < NB && blk2_units_before_row(B + 1, T) <= u) ++B;
-  long rem = u - blk2_units_before_row(B, T);
-  const int row0 = (int)(B << kOrdShift);                               // first tile row (and first tile column) of the diagonal super-block
-  const int w = (T - row0) < (1 << kOrdShift) ? (T - row0) : (1 << kOrdShift);
-  const int sP = (w + 1) / 2;                                           // row pairs of this super-row
-  const long tri = (long)sP * w - (long)sP * (sP - 1);
-  if (rem < tri) {                                                      // diagonal super-block: pair lp has the columns 2 lp .. w - 1
-    int lp = 0;
-    while (lp + 1 < sP && (long)(lp + 1) * w - (long)(lp + 1) * lp <= rem) ++lp;
-    const long before = (long)lp * w - (long)lp * (lp - 1);
-    p = (int)(B * kOrd2Pairs) + lp;
-    J = row0 + 2 * lp + (int)(rem - before);
-    return;
-  }
-  rem -= tri;
-  const int col0 = row0 + (1 << kOrdShift);                             // first column right of the diagonal super-block
-  const long per = (long)sP << kOrdShift;                               // units of a full-width super-block
-  const long q = rem / per;
-  const int c0 = col0 + (int)(q << kOrdShift);
-  const int wQ = (T - c0) < (1 << kOrdShift) ? (T - c0) : (1 << kOrdShift);
-  const long rem2 = rem - q * per;
-  const int lp = (int)(rem2 / wQ);
-  p = (int)(B * kOrd2Pairs) + lp;
-  J = c0 + (int)(rem2 - (long)lp * wQ);
-}
-
-__device__ __forceinline__ void unit2_next(int order, int T, int& p, int& J) {
-  if (order == 0) {
-    if (++J < T) return;
-    ++p;
-    J = 2 * p;
-    return;
-  }
-  const int B = p / kOrd2Pairs, Q = J >> kOrdShift;
-  const int col_end = ((Q + 1) << kOrdShift) < T ? ((Q + 1) << kOrdShift) : T;
-  const int P = (T + 1) / 2;
-  const int pair_end = (B + 1) * kOrd2Pairs < P ? (B + 1) * kOrd2Pairs : P;
-  if (++J < col_end) return;                                            // same pair, same super-block
-  if (++p < pair_end) { J = (Q == B) ? 2 * p : (Q << kOrdShift); return; }   // next pair of the super-block
-  if (((Q + 1) << kOrdShift) < T) { p = B * kOrd2Pairs; J = (Q + 1) << kOrdShift; return; }   // next super-block of the super-row
-  p = (B + 1) * kOrd2Pairs;                                             // next super-row: its diagonal super-block
-  J = 2 * p;
-}
 
 template <int KIND, bool WALL>
 __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(kSymWavesPerEu, kSymWavesPerEu))) void sym2t_kernel(const SymArgs a) {

@@ -23,7 +23,9 @@
 // faster than fp64 on this chip (profiles/r1_ubench_fp64_issue_rates.txt: 785 vs 486 G wave-instr/s): 1.5-1.6x the fp64 kernel.
 #pragma once
 #include "pair_blocks32.h"
+#include "sym_force_kernels.h"
 #include "sym_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force32_kernel(const SymFo
       const float ir = __builtin_amdgcn_rsqf(r2);
       const float r = r2 * ir;
       const float two_a = RADII ? ri + q.w : two_a0;
-      // branch-free as pair_force (sym_kernels.h): exponent 0 exactly for r <= 2a, exp2(0) = 1, min(1/r, 1e25) = 1/r beyond
+      // branch-free as pair_force (sym_force_kernels.h): exponent 0 exactly for r <= 2a, exp2(0) = 1, min(1/r, 1e25) = 1/r beyond
       const float e = __builtin_amdgcn_exp2f(__builtin_fminf((two_a - r) * inv_b_log2e, 0.0f));
       const float f0 = -eps_over_b * (e * __builtin_fminf(ir, 1e25f));
       const float fx = f0 * dx, fy = f0 * dy, fz = f0 * dz;

@@ -21,6 +21,7 @@
 // accumulators and finalize kernel as sym_kernel; results agree to rounding (atomic arrival order).
 #pragma once
 #include "sym_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 

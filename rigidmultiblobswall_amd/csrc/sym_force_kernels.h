@@ -1,0 +1,172 @@
+// sym_force_kernels.h -- symmetric blob-blob force sweep (gfx950, fp64).
+//
+// F_ij = -F_ji, so each unordered pair is evaluated once (one rsqrt + one exp) and applied with opposite signs.  Same
+// tile-pair rotation, LDS accumulation and static step schedule (sym_schedule.h) as sym_kernel; tile culling by the
+// range of the exponential.  multi_bodies/forces_numba.py:12-55 semantics.
+#pragma once
+#include "pair_ops.h"
+#include "sym_schedule.h"
+
+namespace rmb {
+
+struct SymForceArgs {
+  const double4* pos;
+  double* acc;          // [3][n_pad], zero on entry, re-zeroed by the finalize kernel
+  double* out;          // [n][3]
+  long n, n_pad;
+  int n_tiles;
+  long n_units;
+  int order, xcd;       // as SymArgs
+  long chunk_steps;     // > 0: steps per strided chunk of a wave; 0: one contiguous range per wave
+  double Lx, Ly, Lz, iLx, iLy, iLz;
+  double eps_over_b, inv_b, two_a;
+  ExpConsts ec;
+  const double* radii;  // RADII variant: one radius per blob, contact distance a_i + a_j (forces_numba.py:73-122)
+  long step_begin, step_end;   // rotation steps [begin, end) of the n_units * 64 this launch covers (pair shard)
+  // Tile culling (uniform radius; open or pseudo-periodic): bounds[T] = (xmin, ymin, zmin, xmax, ymax, zmax) of tile T
+  // (tile_bounds_kernel), cull2 = (2a + 750 b)^2.  A tile pair whose boxes are further apart than that holds only
+  // pairs with (r - 2a)/b > 750, for which exp underflows to exactly 0 here (exp_nonpositive) and in the reference
+  // (exp(-745.2) is the smallest denormal): skipping the unit changes no bit of the result.  nullptr = no culling.
+  const double* bounds;
+  double cull2;
+  // Spatially sorted configuration (rmb_sort.hip): `pos` is then the sorted copy and perm[s] the caller's index of
+  // sorted slot s; the finalize kernel writes slot s to out[perm[s]].  nullptr = the caller's order.
+  const unsigned* perm;
+};
+
+// f0(r) dr for one pair; dr = r_j - r_i (minimal image), two_a = contact distance of the pair.
+// Returns the force ON i; the force on j is minus it.
+template <bool PERIODIC>
+__device__ __forceinline__ void pair_force(const SymForceArgs& a, double two_a, double dx, double dy, double dz, double& fx,
+                                           double& fy, double& fz) {
+  if constexpr (PERIODIC) {
+    if (a.Lx > 0) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
+    if (a.Ly > 0) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
+    if (a.Lz > 0) dz = wrap_nearest_pad_safe(dz, a.Lz, a.iLz);
+  }
+  const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
+  const double ir = rsqrt_f64(r2);
+  const double r = r2 * ir;
+  // far: -(eps/b) exp(-(r-2a)/b) / r ;  near (r <= 2a): -(eps/b) / max(r, 1e-25) = -(eps/b) min(1/r, 1e25)
+  // Branch-free: x = min((2a - r)/b, 0) is 0 exactly for r <= 2a (and for r = NaN at coincident points, fmin keeps
+  // the number), exp(0) = 1 exactly, and min(1/r, 1e25) = 1/r for every r > 2a -- one expression serves both ranges.
+  const double x = fmin((two_a - r) * a.inv_b, 0.0);
+  const double e = exp_nonpositive(a.ec, x);
+  const double f0 = -a.eps_over_b * (e * fmin(ir, 1e25));
+  fx = f0 * dx; fy = f0 * dy; fz = f0 * dz;
+}
+
+template <bool PERIODIC, bool RADII = false>
+__global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForceArgs a) {
+  __shared__ double4 rec_all[kSymWaves][64];
+  __shared__ double accj_all[kSymWaves][3 * 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double4* rec = rec_all[wave];
+  double* accj = accj_all[wave];
+  const long n_waves = (long)gridDim.x * kSymWaves;
+  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
+  const long s_total = a.step_end - a.step_begin;
+  const long spw = a.chunk_steps > 0 ? a.chunk_steps : (s_total + n_waves - 1) / n_waves;
+  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
+  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
+  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
+  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
+  for (long chunk = w;; chunk += n_waves) {
+  long s = a.step_begin + chunk * spw;
+  if (s >= a.step_end) break;
+  long s_end = s + spw;
+  if (s_end > a.step_end) s_end = a.step_end;
+  int I = 0, J = 0;
+  if (s < s_end) unit_seek(a.order, s >> 6, a.n_tiles, I, J);
+  int I_cur = -1;
+  long i = 0;
+  bool vi_ok = false;
+  double xi = 0, yi = 0, zi = 0, ri = 0;
+  double ax = 0, ay = 0, az = 0;
+  while (s < s_end) {
+    const int k0 = (int)(s & 63);
+    const long left = s_end - s;
+    const int k1 = (left < 64 - k0) ? (int)(k0 + left) : 64;
+    s += k1 - k0;
+    if (a.bounds != nullptr && I != J &&
+        tile_gap2(a.bounds, I, J, PERIODIC ? a.Lx : 0.0, PERIODIC ? a.Ly : 0.0, PERIODIC ? a.Lz : 0.0) > a.cull2) {
+      // every pair of this unit is beyond the range of the exponential: contributes exactly zero
+      if (k1 == 64) {
+        unit_next(a.order, a.n_tiles, I, J);
+      }
+      continue;
+    }
+    if (I != I_cur) {
+      if (I_cur >= 0 && vi_ok) {
+        __hip_atomic_fetch_add(&a.acc[i], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      I_cur = I;
+      i = 64L * I + lane;
+      vi_ok = i < a.n;
+      xi = 1e100; yi = 1e100; zi = 1e100;
+      if (vi_ok) { const double4 p = a.pos[i]; xi = p.x; yi = p.y; zi = p.z; }
+      if constexpr (RADII) ri = vi_ok ? a.radii[i] : 0.0;
+      ax = 0.0; ay = 0.0; az = 0.0;
+    }
+    {
+      const long j = 64L * J + lane;
+      double4 p = make_double4(-1e100, -1e100, -1e100, 0.0);
+      if (j < a.n) p = a.pos[j];
+      if constexpr (RADII) p.w = (j < a.n) ? a.radii[j] : 0.0;   // w is free here: forces use unclamped positions (b = 1)
+      rec[lane] = p;
+      accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool diag = (I == J);
+    for (int k = (diag && k0 < 1) ? 1 : k0; k < k1; ++k) {
+      const int jj = (lane + k) & 63;
+      const double4 q = rec[jj];
+      double fx, fy, fz;
+      pair_force<PERIODIC>(a, RADII ? ri + q.w : a.two_a, q.x - xi, q.y - yi, q.z - zi, fx, fy, fz);
+      ax += fx; ay += fy; az += fz;
+      if (!diag) {   // wave-uniform
+        // the LDS slab collects +f (ds_add_f64 has no negate modifier: -f would cost a v_xor + v_mov per component
+        // and step); the sign of the reaction goes into the flush below
+        __hip_atomic_fetch_add(&accj[jj], fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __hip_atomic_fetch_add(&accj[64 + jj], fy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __hip_atomic_fetch_add(&accj[128 + jj], fz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      }
+    }
+    if (!diag) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const long j = 64L * J + lane;
+      if (j < a.n) {
+        __hip_atomic_fetch_add(&a.acc[j], -accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&a.acc[a.n_pad + j], -accj[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + j], -accj[128 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (k1 == 64) {
+      unit_next(a.order, a.n_tiles, I, J);
+    }
+  }
+  if (I_cur >= 0 && vi_ok) {
+    __hip_atomic_fetch_add(&a.acc[i], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  }   // chunks
+}
+
+static __global__ __launch_bounds__(256) void sym_force_finalize_kernel(const SymForceArgs a) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const long o = a.perm ? (long)a.perm[i] : i;
+  a.out[3 * o] = a.acc[i]; a.out[3 * o + 1] = a.acc[a.n_pad + i]; a.out[3 * o + 2] = a.acc[2 * a.n_pad + i];
+  a.acc[i] = 0.0; a.acc[a.n_pad + i] = 0.0; a.acc[2 * a.n_pad + i] = 0.0;
+}
+
+}  // namespace rmb

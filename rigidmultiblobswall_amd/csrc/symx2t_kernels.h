@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "sym2t_kernels.h"
+#include "sym_schedule.h"
 #include "symx_kernels.h"
 
 namespace rmb {

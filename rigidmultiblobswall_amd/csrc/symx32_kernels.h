@@ -14,6 +14,7 @@
 #include "pair_blocks32.h"
 #include "symx_kernels.h"
 #include "sym32_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 

@@ -7,6 +7,7 @@
 // vectors (OpKindK<.., 4>) and 47 KB for three -- two resp. three workgroups per CU, i.e. two or three waves per SIMD
 // where the registers would allow three or four.  One slab per workgroup is 15 + 2 x 6 KB: LDS stops limiting residency.
 #pragma once
+#include "sym_schedule.h"
 #include "symx_kernels.h"
 
 namespace rmb {

@@ -26,6 +26,7 @@
 //   OP::self<WALL>(k, zi, vi, ui)                        the i == j term, added once per target in finalize
 #pragma once
 #include "sym_kernels.h"
+#include "sym_schedule.h"
 
 namespace rmb {
 

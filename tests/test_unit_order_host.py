@@ -1,11 +1,15 @@
-"""Host-side check of the device helpers that decide WHICH tile pair a wave works on (csrc/sym_kernels.h: unit_seek /
-unit_next for the row-major and the blocked order, xcd_swizzle): the functions are plain integer arithmetic, so they are
-compiled for the host (g++, `__device__` defined away) straight from the header and checked exhaustively -- seek and
-next agree, every tile pair I <= J is visited exactly once, the XCD numbering is a bijection."""
+"""Host-side check of the device helpers that decide WHICH tile pair a wave works on (csrc/sym_schedule.h: unit_seek /
+unit_next for the row-major and the blocked order, xcd_swizzle): the functions are plain integer arithmetic, so the
+header is included in a host program (g++, `__device__` defined away) and checked exhaustively -- seek and next agree,
+every tile pair I <= J is visited exactly once, the XCD numbering is a bijection."""
 import os
 import subprocess
 
 from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "rigidmultiblobswall_amd", "csrc")
+PRELUDE = ("#include <cmath>\n#include <cstdio>\n#include <set>\n#include <utility>\n#include <vector>\n"
+           "#define __device__\n#define __host__\n#define __forceinline__ inline\n#include \"sym_schedule.h\"\nusing namespace rmb;\n")
 
 HARNESS = r'''
 int main() {
@@ -53,15 +57,11 @@ int main() {
 
 
 def test_unit_order_and_xcd_numbering(tmp_path):
-  src = open(os.path.join(ROOT, "rigidmultiblobswall_amd", "csrc", "sym_kernels.h")).read()
-  begin = src.index("__device__ __forceinline__ void unit_to_tiles(long u, int T, int& I, int& J) {")
-  end = src.index("template <int KIND, bool WALL, bool PERIODIC>\n__global__", begin)
-  code = ("#include <cmath>\n#include <cstdio>\n#include <set>\n#include <utility>\n#include <vector>\n"
-          "#define __device__\n#define __forceinline__ inline\n" + src[begin:end] + HARNESS)
+  code = PRELUDE + HARNESS
   cpp, exe = str(tmp_path / "unit_order.cpp"), str(tmp_path / "unit_order")
   with open(cpp, "w") as fh:
     fh.write(code)
-  subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, cpp])
+  subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", CSRC, "-o", exe, cpp])
   res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
   assert res.returncode == 0 and "problems 0" in res.stdout, res.stdout + res.stderr
 
@@ -111,16 +111,12 @@ int main() {
 
 
 def test_row_pair_unit_order(tmp_path):
-  """The unit grid of the two-targets-per-lane kernel (csrc/sym2t_kernels.h: unit2_seek / unit2_next, plain and blocked):
+  """The unit grid of the two-targets-per-lane kernel (csrc/sym_schedule.h: unit2_seek / unit2_next, plain and blocked):
   every (row pair p, tile J >= 2p) exactly once, seek and next agree."""
-  src = open(os.path.join(ROOT, "rigidmultiblobswall_amd", "csrc", "sym2t_kernels.h")).read()
-  begin = src.index("// ---- unit order ----")
-  end = src.index("template <int KIND, bool WALL>\n__global__", begin)
-  code = ("#include <cmath>\n#include <cstdio>\n#include <set>\n#include <utility>\n#include <vector>\n"
-          "#define __device__\n#define __host__\n#define __forceinline__ inline\nconstexpr int kOrdShift = 5;\n" + src[begin:end] + HARNESS2)
+  code = PRELUDE + HARNESS2
   cpp, exe = str(tmp_path / "unit2_order.cpp"), str(tmp_path / "unit2_order")
   with open(cpp, "w") as fh:
     fh.write(code)
-  subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, cpp])
+  subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", CSRC, "-o", exe, cpp])
   res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
   assert res.returncode == 0 and "problems 0" in res.stdout, res.stdout + res.stderr
