@@ -19,6 +19,14 @@
  *     reference: z_eff = max(z, a) (mobility.py:52-64) and u = B M(z_eff) B v with
  *     B_ii = z_i/a for z_i < a (mobility.py:67-84, :1150-1163).  wall == 0: unbounded RPY, no clamp
  *     (mobility.py:1119-1129).
+ *   - free surface: with context option "free_surface" = 1, `wall` != 0 in rmb_set_positions* means a
+ *     stress-free surface at z = 0 instead of a no-slip wall (raw heights, no clamp, no B).  On such a
+ *     configuration RMB_TT is the free-surface product (RMB_TT_FREE_SURFACE), the dense per-body blocks
+ *     and the rigid-body operator / Arnoldi / Lanczos / GMRES entry points carry the image of
+ *     mobility_numba.py:1840-1926; tr / rt / rr / tt_tr, in_plane, the two-vector pass and every
+ *     rmb_op but RMB_OP_TT_MULTI (one sweep per vector) return RMB_ERR_STATE: the reference has no
+ *     rotational products above a free surface.  (An option, not wall == 2: every non-zero `wall` has
+ *     always meant the no-slip wall here.)
  *   - every function returns 0 on success, a negative rmb_status otherwise; rmb_last_error()
  *     gives a message for the calling thread.  The reference defines no error codes (failures
  *     surface as Python exceptions from pycuda); the Python shim raises RuntimeError on non-zero.

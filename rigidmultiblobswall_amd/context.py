@@ -103,8 +103,19 @@ class MobilityContext(object):
     _lib.check(self._lib.rmb_ctx_get_option(self._h, key.encode(), ctypes.byref(v)))
     return int(v.value)
 
+  supports_free_surface = True     # set_positions(wall="free_surface"), see there
+
   def set_positions(self, r_vectors, a, periodic_length=None, wall=True):
-    """r_vectors: numpy (N,3)/(3N,) or a CUDA torch float64 tensor (stays on device)."""
+    """r_vectors: numpy (N,3)/(3N,) or a CUDA torch float64 tensor (stays on device).
+    wall: True (no-slip wall at z = 0: clamped heights, B damping), False (unbounded) or "free_surface": a stress-free
+    surface at z = 0 (context option "free_surface" + wall = 1 in the C ABI).  On such a configuration kind "tt" is the
+    free-surface product and the dense blocks and the rigid-body solver calls carry its image; "tr" / "rt" / "rr" /
+    "tt_tr", in_plane and the multi-block operations raise (RMB_ERR_STATE)."""
+    free_surface = isinstance(wall, str)
+    if free_surface and wall != "free_surface":
+      raise ValueError("wall must be True, False or \"free_surface\"")
+    if free_surface != bool(self._options_set.get("free_surface", 0)) and wall:
+      self.set_option("free_surface", 1 if free_surface else 0)
     L = _as_f64(np.zeros(3) if periodic_length is None else periodic_length, 3)
     if _is_torch_cuda(r_vectors):
       r = r_vectors.contiguous().view(-1)
@@ -120,7 +131,7 @@ class MobilityContext(object):
     self.n = n
     self.n_targets = n
     self.target_range = (0, n)
-    self._geometry = (int(n), float(a), tuple(float(x) for x in L), bool(wall))
+    self._geometry = (int(n), float(a), tuple(float(x) for x in L), wall if free_surface else bool(wall))
 
   def set_target_range(self, begin, end):
     _lib.check(self._lib.rmb_set_target_range(self._h, int(begin), int(end)))

@@ -22,7 +22,10 @@ struct DenseArgs {
   PairConsts k;
 };
 
-template <bool WALL>
+// BND: rmb::Boundary.  Above a free surface entry (i, j) is RPY(d) + RPY(R) P with R = (d_x, d_y, z_i + z_j) and
+// P = diag(1, 1, -1) (mobility_numba.py:1840-1926: the image block with its z column negated, the overlapping-RPY branch for
+// the image too; self block 4/(3a) I + the blob's own image at R = (0, 0, 2 z_i)), on raw heights.
+template <int BND>
 __global__ __launch_bounds__(256) void body_dense_tt_kernel(const DenseArgs a) {
   const long body = blockIdx.x;
   const long base = a.first_blob[body];
@@ -38,8 +41,9 @@ __global__ __launch_bounds__(256) void body_dense_tt_kernel(const DenseArgs a) {
     for (int c = 0; c < 3; ++c) {
       const double vx = c == 0 ? 1.0 : 0.0, vy = c == 1 ? 1.0 : 0.0, vz = c == 2 ? 1.0 : 0.0;
       Vec3 u = {0.0, 0.0, 0.0};
-      if (i == j) self_term<KIND_TT, WALL>(a.k, pi.z, vx, vy, vz, 0, 0, 0, u);
-      else pair_apply<KIND_TT, WALL>(a.k, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, pi.z, pj.z, vx, vy, vz, 0, 0, 0, u);
+      if (i == j) tt_self_term<BND>(a.k, pi.z, vx, vy, vz, u);
+      else pair_apply<BND == BND_FREE ? KIND_TT_FREE : KIND_TT, BND == BND_WALL>(a.k, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, pi.z, pj.z, vx, vy, vz,
+                                                                                  0, 0, 0, u);
       M[(long)(3 * i + 0) * ld + 3 * j + c] = u.x * sc;
       M[(long)(3 * i + 1) * ld + 3 * j + c] = u.y * sc;
       M[(long)(3 * i + 2) * ld + 3 * j + c] = u.z * sc;

@@ -264,6 +264,18 @@ __device__ __forceinline__ void self_term(const PairConsts& k, double zi, double
   }
 }
 
+// Boundary of the resident configuration as the kernels above the pair sweeps see it (dense per-body blocks, the finishing
+// launches of the rigid-body operator): unbounded, no-slip wall (clamped heights, B damping), or stress-free surface at
+// z = 0 (raw heights).
+enum Boundary : int { BND_NONE = 0, BND_WALL = 1, BND_FREE = 2 };
+
+// translation-translation self term of boundary BND
+template <int BND>
+__device__ __forceinline__ void tt_self_term(const PairConsts& k, double zi, double vx, double vy, double vz, Vec3& u) {
+  if constexpr (BND == BND_FREE) self_term<KIND_TT_FREE, false>(k, zi, vx, vy, vz, 0, 0, 0, u);
+  else                           self_term<KIND_TT, BND == BND_WALL>(k, zi, vx, vy, vz, 0, 0, 0, u);
+}
+
 // exp(x) for x <= 0 in fp64 without ocml: n = rint(x log2 e), t = x - n ln2 (two-piece ln2), degree-13 Taylor
 // polynomial in t (|t| <= ln2/2: truncation 4e-18), result = ldexp(p, n) (v_ldexp_f64 underflows gradually to 0).
 // The coefficients travel as kernel arguments (SGPRs) so that every Horner step is one v_fma_f64 with a scalar

@@ -8,10 +8,25 @@
 
 namespace rmbi {
 
+namespace {
+// On a free-surface context RMB_TT is the free-surface product; nothing else exists above that boundary (the reference has
+// no rotational products there: mobility_numba.py has free_surface_mobility_trans_times_force only)
+int free_surface_kind(int* kind, int in_plane) {
+  if (*kind != rmb::KIND_TT && *kind != rmb::KIND_TT_FREE)
+    return fail(RMB_ERR_STATE, "free-surface context: only RMB_TT exists above a free surface (no tr / rt / rr / tt_tr products)");
+  if (in_plane) return fail(RMB_ERR_STATE, "free-surface context: in_plane products are not served above a free surface here (load the configuration with wall = 0 and use RMB_TT_FREE_SURFACE)");
+  *kind = rmb::KIND_TT_FREE;
+  return 0;
+}
+}  // namespace
+
 int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, const double* v2, double eta,
                        double* out) {
   if (int rc = check_ready(c)) return rc;
   if (kind < 0 || kind >= rmb::KIND_COUNT) return fail(RMB_ERR_ARG, "kind must be 0..5");
+  if (c->free_surface) {
+    if (int rc = free_surface_kind(&kind, in_plane)) return rc;
+  }
   if (kind == rmb::KIND_TT_FREE && c->wall)
     return fail(RMB_ERR_STATE, "RMB_TT_FREE_SURFACE uses raw heights: call rmb_set_positions with wall = 0");
   const long n_tgt = c->tgt_end - c->tgt_begin;
@@ -79,6 +94,9 @@ int force_device_impl(rmb_ctx* c, double eps, double b, double blob_radius, doub
 // kinds with in_plane go through matvec_op_impl's *_MULTI operations); the public rmb_matvec_pairshard_device passes 0.
 int matvec_pairshard_impl(rmb_ctx* c, int kind, int in_plane, const double* v, double eta, double* out, long shard, long nshards) {
   if (int rc = check_ready(c)) return rc;
+  if (c->free_surface && kind >= 0 && kind < rmb::KIND_COUNT) {
+    if (int rc = free_surface_kind(&kind, in_plane)) return rc;
+  }
   if ((kind < 0 || kind > rmb::KIND_RR) && kind != rmb::KIND_TT_FREE)
     return fail(RMB_ERR_ARG, "pair sharding is implemented for RMB_TT / TR / RT / RR / TT_FREE_SURFACE (RMB_TT_TR: rmb_matvec_op_pairshard_device)");
   if (kind == rmb::KIND_TT_FREE && c->wall)
@@ -125,6 +143,15 @@ int matvec_op_impl(rmb_ctx* c, int op, int in_plane, int n_in, const double* con
   for (int v = 0; v < n_out; ++v) if (!out[v]) return fail(RMB_ERR_ARG, "null output vector");
   if (c->n == 0) return 0;
   RMB_HIP(hipSetDevice(c->device));
+  if (c->free_surface) {
+    // no fused multi-vector pass above a free surface: RMB_OP_TT_MULTI is one free-surface sweep per vector, the other
+    // operations need rotational blocks the boundary does not have
+    if (op != RMB_OP_TT_MULTI) return fail(RMB_ERR_STATE, "free-surface context: only RMB_OP_TT_MULTI is served (one sweep per vector); no rotational blocks above a free surface");
+    for (int v = 0; v < n_in; ++v)
+      if (int rc = nshards > 1 ? matvec_pairshard_impl(c, rmb::KIND_TT, in_plane, in[v], eta, out[v], shard, nshards)
+                               : matvec_device_impl(c, rmb::KIND_TT, in_plane, in[v], nullptr, eta, out[v])) return rc;
+    return 0;
+  }
   // a pair shard always writes all n targets, whatever target range is set (as rmb_matvec_pairshard_device)
   if (c->opt_deterministic == 2 && (nshards > 1 || sym_applies(c))) return symx_det_device(c, sx, in, out, eta, in_plane, shard, nshards);
   if (sym_applies(c) || nshards > 1) return symx_device(c, sx, in, out, eta, in_plane, shard, nshards);
@@ -229,6 +256,7 @@ int rmb_matvec2_pairshard_device(rmb_ctx* c, int kind, const double* vec_a, cons
                                  double* out_a, double* out_b, long shard, long nshards) {
   if (int rc = check_ready(c)) return rc;
   if (kind != rmb::KIND_TT) return fail(RMB_ERR_ARG, "two-vector products exist for RMB_TT only");
+  if (c->free_surface) return fail(RMB_ERR_STATE, "free-surface context: no two-vector pass above a free surface (use rmb_matvec_device per vector)");
   if (!vec_a || !vec_b || !out_a || !out_b) return fail(RMB_ERR_ARG, "null vector / output pointer");
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   if (nshards < 1 || shard < 0 || shard >= nshards) return fail(RMB_ERR_ARG, "bad shard");

@@ -69,6 +69,9 @@ struct rmb_ctx {
   double a = 0.0;
   double L[3] = {0, 0, 0};
   int wall = 0;
+  int free_surface = 0;          // the configuration was loaded with wall != 0 under option "free_surface": raw heights (wall = 0 above),
+                                 // kind tt is the free-surface product
+  long opt_free_surface = 0;     // rmb_set_positions*(wall != 0) means a stress-free surface at z = 0, not a no-slip wall
   bool have_positions = false;
   long tgt_begin = 0, tgt_end = 0;
   // device memory
@@ -344,7 +347,10 @@ int sym_device(rmb_ctx* c, int kind, const double* v, double eta, double* out, l
 int sym2_device(rmb_ctx* c, const double* va, const double* vb, double eta, double* out_a, double* out_b, long shard = 0,
                 long nshards = 1);
 int symx_device(rmb_ctx* c, int op, const double* const* in, double* const* out, double eta, int in_plane, long shard,
-                long nshards, int accumulate_mask = 0, const SymConf* conf_in = nullptr);
+                long nshards, int accumulate_mask = 0, const SymConf* conf_in = nullptr, bool no_finalize = false);
+// the raw sums of the resident boundary's tt product left in the accumulators (sym_device / symx_device with no_finalize):
+// KIND_TT, or SX_FREE on a free-surface context
+int tt_raw_sums_device(rmb_ctx* c, const double* v, double eta, double* out);
 int symx_det_device(rmb_ctx* c, int op, const double* const* in, double* const* out, double eta, int in_plane,
                     long shard = 0, long nshards = 1);
 int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, double* out, const double* radii, long shard,

@@ -421,9 +421,9 @@ struct OpFinArgs {
 };
 
 // Thread l < n_b finishes blob i = body n_b + l exactly as sym_finalize_kernel does (self term of the B-damped lambda,
-// scaling by b_i / (8 pi eta)), subtracts row i of K U, and contributes its three rows of K^T lambda to a fixed-order
+// scaling by b_i / (8 pi eta); above a free surface the self term symx_finalize_kernel applies for SX_FREE), subtracts row i of K U, and contributes its three rows of K^T lambda to a fixed-order
 // reduction over the body.
-template <bool WALL>
+template <int BND>      // rmb::Boundary
 __global__ __launch_bounds__(256) void rigid_operator_finish_kernel(const OpFinArgs a) {
   extern __shared__ double wl[];          // 3 n_b + 6: the body's slices of the result (only with a.part)
   __shared__ double part[4][6];
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256) void rigid_operator_finish_kernel(const OpFinA
     const double4 p = a.pos[i];
     const double b = p.w;
     const double lx = a.x[3 * i], ly = a.x[3 * i + 1], lz = a.x[3 * i + 2];
-    rmb::self_term<rmb::KIND_TT, WALL>(a.k, p.z, lx * b, ly * b, lz * b, 0, 0, 0, acc);
+    rmb::tt_self_term<BND>(a.k, p.z, lx * b, ly * b, lz * b, acc);
     const double sc = a.prefactor * b;
     const double* U = a.x + n3 + 6 * body;
     const double* Kr = a.K + (body * 3 * a.n_b + 3 * l) * 6;
@@ -510,7 +510,7 @@ struct LanFinArgs {
   double* part;
 };
 
-template <bool WALL>
+template <int BND>      // rmb::Boundary
 __global__ __launch_bounds__(1024) void lanczos_finish_kernel(const LanFinArgs a) {
   extern __shared__ double xl[];          // 3 n_b finished entries, 3 n_b row sums (two_by_two_rows), 3 n_b results (with a.part)
   const long body = blockIdx.x;
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(1024) void lanczos_finish_kernel(const LanFinArgs a
     a.acc[i] = 0.0; a.acc[a.n_pad + i] = 0.0; a.acc[2 * a.n_pad + i] = 0.0;     // ready for the next product
     const double4 p = a.pos[i];
     const double b = p.w;
-    rmb::self_term<rmb::KIND_TT, WALL>(a.k, p.z, a.x[3 * i] * b, a.x[3 * i + 1] * b, a.x[3 * i + 2] * b, 0, 0, 0, acc);
+    rmb::tt_self_term<BND>(a.k, p.z, a.x[3 * i] * b, a.x[3 * i + 1] * b, a.x[3 * i + 2] * b, acc);
     const double sc = a.prefactor * b;
     xl[3 * l] = acc.x * sc; xl[3 * l + 1] = acc.y * sc; xl[3 * l + 2] = acc.z * sc;
   }
@@ -609,8 +609,9 @@ int plain_tt_with_dots(rmb_ctx* c, const double* v_dev, double eta, double* out_
   *tiles_done = 0;
   const long n = c->n, n_tiles = (n + 63) / 64;
   const bool periodic = c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0;
+  // (free-surface contexts take the plain product: this finishing launch has wall / unbounded instances only)
   if (!(c->opt_gmres_fuse_dots && sym_applies(c) && !periodic && c->opt_deterministic == 0 && c->opt_precision == 64 && c->tgt_begin == 0 &&
-        c->tgt_end == n && n_tiles <= kKrBodyPartialsMax))
+        c->tgt_end == n && n_tiles <= kKrBodyPartialsMax && !c->free_surface))
     return matvec_device_impl(c, rmb::KIND_TT, 0, v_dev, nullptr, eta, out_dev);
   PlainFinArgs a;
   if (int rc = krylov_body_partials(c, 3 * n, &a.part)) return rc;
@@ -648,7 +649,7 @@ int lanczos_step_impl(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_de
   if (c->opt_lanczos_fuse_finish && sym_applies(c) && !periodic && c->opt_deterministic == 0 && c->opt_precision == 64 && c->tgt_begin == 0 && c->tgt_end == n &&
       n_b <= 256) {
     // the pair sweep with the raw sums left in the accumulators, then ONE finishing launch (finalize + L_b^-1)
-    if (int rc = sym_device(c, rmb::KIND_TT, pv_dev, eta, mw_dev, 0, 1, false, true)) return rc;
+    if (int rc = tt_raw_sums_device(c, pv_dev, eta, mw_dev)) return rc;
     LanFinArgs a;
     a.pos = (const double4*)c->pos.p; a.x = pv_dev; a.acc = (double*)c->symbuf.p; a.linv = BlockRef{Linv_dev, nn * nn, nn, 1}; a.out = d_dev;
     a.n = n; a.n_pad = 64 * ((n + 63) / 64); a.n_b = (int)n_b;
@@ -665,8 +666,9 @@ int lanczos_step_impl(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_de
       dots_bodies = n_bodies;
     }
     const size_t lds = (size_t)(3 * nn) * sizeof(double);
-    if (c->wall) hipLaunchKernelGGL(lanczos_finish_kernel<true>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
-    else         hipLaunchKernelGGL(lanczos_finish_kernel<false>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    if (c->free_surface) hipLaunchKernelGGL(lanczos_finish_kernel<rmb::BND_FREE>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    else if (c->wall)    hipLaunchKernelGGL(lanczos_finish_kernel<rmb::BND_WALL>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    else                 hipLaunchKernelGGL(lanczos_finish_kernel<rmb::BND_NONE>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
     RMB_HIP(hipGetLastError());
   } else {
     if (int rc = matvec_device_impl(c, rmb::KIND_TT, 0, pv_dev, nullptr, eta, mw_dev)) return rc;
@@ -791,7 +793,7 @@ int rigid_operator_impl(rmb_ctx* c, long n_bodies, long n_b, const double* K_dev
   const bool periodic = c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0;
   if (sym_applies(c) && !periodic && c->opt_deterministic == 0 && c->opt_precision == 64) {
     // pair sweep with the raw sums left in the accumulators, then ONE finishing launch
-    if (int rc = sym_device(c, rmb::KIND_TT, x_dev, eta, out_dev, 0, 1, false, true)) return rc;
+    if (int rc = tt_raw_sums_device(c, x_dev, eta, out_dev)) return rc;
     OpFinArgs a;
     a.pos = (const double4*)c->pos.p; a.x = x_dev; a.K = K_dev; a.acc = (double*)c->symbuf.p; a.out = out_dev;
     a.n = n; a.n_pad = 64 * ((n + 63) / 64); a.n_bodies = n_bodies; a.n_b = (int)n_b;
@@ -805,8 +807,9 @@ int rigid_operator_impl(rmb_ctx* c, long n_bodies, long n_b, const double* K_dev
       threads = 256;                                    // four waves share the basis rows
       lds = (size_t)(3 * n_b + 6) * sizeof(double);
     }
-    if (c->wall) hipLaunchKernelGGL(rigid_operator_finish_kernel<true>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
-    else         hipLaunchKernelGGL(rigid_operator_finish_kernel<false>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    if (c->free_surface) hipLaunchKernelGGL(rigid_operator_finish_kernel<rmb::BND_FREE>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    else if (c->wall)    hipLaunchKernelGGL(rigid_operator_finish_kernel<rmb::BND_WALL>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
+    else                 hipLaunchKernelGGL(rigid_operator_finish_kernel<rmb::BND_NONE>, dim3((unsigned)n_bodies), dim3(threads), lds, c->stream, a);
     RMB_HIP(hipGetLastError());
     if (a.part && dots_done) *dots_done = true;
     return 0;

@@ -70,17 +70,22 @@ int force_sweep_device(rmb_ctx* c, double eps, double b, double blob_radius, dou
 }
 
 int pack_positions(rmb_ctx* c, const double* r_dev, long n, double a, const double* L, int wall) {
+  // option "free_surface": the boundary at z = 0 is a stress-free surface instead of a no-slip wall -- raw heights, no
+  // clamp, no B damping; every kernel instance chosen by c->wall is then the unbounded one, the image comes from the
+  // free-surface operation (c->free_surface)
+  const bool free_surface = wall && c->opt_free_surface;
   if (int rc = c->pos.reserve((size_t)(n > 0 ? n : 1) * sizeof(double4))) return rc;
   if (n > 0) {
     hipLaunchKernelGGL(rmb::pack_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, r_dev, n,
-                       a, wall ? 1 : 0, (double4*)c->pos.p);
+                       a, wall && !free_surface ? 1 : 0, (double4*)c->pos.p);
     RMB_HIP(hipGetLastError());
   }
   c->n = n;
   c->a = a;
   c->tile_bounds_valid = false;
   for (int k = 0; k < 3; ++k) c->L[k] = L ? L[k] : 0.0;
-  c->wall = wall ? 1 : 0;
+  c->wall = wall && !free_surface ? 1 : 0;
+  c->free_surface = free_surface ? 1 : 0;
   c->tgt_begin = 0;
   c->tgt_end = n;
   c->have_positions = true;
@@ -137,8 +142,9 @@ int body_dense_device(rmb_ctx* c, const long* first_blob_dev, long n_bodies, int
   if (ysplit < 1) ysplit = 1;
   if (ysplit > 4096) ysplit = 4096;
   const dim3 grid((unsigned)n_bodies, (unsigned)ysplit);
-  if (c->wall) hipLaunchKernelGGL(rmb::body_dense_tt_kernel<true>, grid, dim3(256), 0, c->stream, a);
-  else         hipLaunchKernelGGL(rmb::body_dense_tt_kernel<false>, grid, dim3(256), 0, c->stream, a);
+  if (c->free_surface) hipLaunchKernelGGL(rmb::body_dense_tt_kernel<rmb::BND_FREE>, grid, dim3(256), 0, c->stream, a);
+  else if (c->wall)    hipLaunchKernelGGL(rmb::body_dense_tt_kernel<rmb::BND_WALL>, grid, dim3(256), 0, c->stream, a);
+  else                 hipLaunchKernelGGL(rmb::body_dense_tt_kernel<rmb::BND_NONE>, grid, dim3(256), 0, c->stream, a);
   RMB_HIP(hipGetLastError());
   return 0;
 }

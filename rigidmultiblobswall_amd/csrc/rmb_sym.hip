@@ -205,12 +205,13 @@ void fill_symx_io(rmb::SymXArgs& a, const SymXEntry& se, const SymConf& cf, cons
 }  // namespace
 
 int symx_device(rmb_ctx* c, int op, const double* const* in, double* const* out, double eta, int in_plane, long shard,
-                long nshards, int accumulate_mask, const SymConf* conf_in) {
+                long nshards, int accumulate_mask, const SymConf* conf_in, bool no_finalize) {
   const SymConf cf = conf_in ? *conf_in : conf_of(c);
   const bool periodic = is_periodic(cf);
   const SymXEntry& se = g_symx[op][cf.wall ? 1 : 0][periodic ? 1 : 0];
   const long n = cf.n;
   if (int rc = sym_accumulators(c, 64 * ((n + 63) / 64))) return rc;
+  if (periodic && no_finalize) return fail(RMB_ERR_STATE, "symx_device: no_finalize is for open boundaries (internal)");
   // Two target blobs per lane (symx2t_kernels.h): fused row, grand, force column, one block on two vectors, and every
   // pseudo-periodic single-vector product.
   SymCandidates k{se.sweep, symx_coop(op, cf.wall != 0, periodic),
@@ -234,7 +235,15 @@ int symx_device(rmb_ctx* c, int op, const double* const* in, double* const* out,
   a.steps_per_wave = ch.steps_per_wave;
   a.accumulate = accumulate_mask;
   a.skip_pairs = (int)c->opt_skip_pairs;
-  return sym_launch(c, ch.kernel, ch.path, ch.plan.blocks, ch.plan.dyn_lds, a, a.k, se.fin, (n + 255) / 256);
+  // no_finalize: the caller finishes the accumulators itself (as sym_device)
+  return sym_launch(c, ch.kernel, ch.path, ch.plan.blocks, ch.plan.dyn_lds, a, a.k, no_finalize ? nullptr : se.fin, (n + 255) / 256);
+}
+
+int tt_raw_sums_device(rmb_ctx* c, const double* v, double eta, double* out) {
+  if (!c->free_surface) return sym_device(c, rmb::KIND_TT, v, eta, out, 0, 1, false, true);
+  const double* in[2] = {v, nullptr};
+  double* outs[1] = {out};
+  return symx_device(c, SX_FREE, in, outs, eta, 0, 0, 1, 0, nullptr, true);
 }
 
 // Deterministic symmetric pass ("deterministic" = 2): same pair arithmetic as symx_device, but whole units per wave and

@@ -22,8 +22,9 @@ def _split(impl):
   return None, impl
 
 
-def hydrodynamic_mode(impl, option):
-  """'single_wall' | 'no_wall' from a mobility implementation string; ValueError for anything else."""
+def hydrodynamic_mode(impl, option, free_surface=False):
+  """'single_wall' | 'no_wall' (| 'free_surface' where the caller runs it: free_surface=True) from a mobility
+  implementation string; ValueError for anything else."""
   if "radii" in impl:
     raise ValueError("%s %r: per-blob radii are served by the source-target products (dispatch.set_mobility_vector_prod), "
                      "not by the time steppers, which assume one blob radius" % (option, impl))
@@ -34,6 +35,8 @@ def hydrodynamic_mode(impl, option):
     return "single_wall"
   if suffix == "no_wall":
     return "no_wall"
+  if suffix == "free_surface" and free_surface:
+    return "free_surface"
   if suffix == "free_surface":
     raise ValueError("%s %r: the time steppers do not run above a free surface (the product itself exists: "
                      "free_surface_mobility_trans_times_force_hip)" % (option, impl))
@@ -42,15 +45,40 @@ def hydrodynamic_mode(impl, option):
 
 def validate(read, uses_dense_blocks=True):
   """Checks every implementation option of a ReadInput deck against `domain`; returns the hydrodynamic mode
-  ('single_wall', 'no_wall' or 'in_plane' as given by `domain`)."""
+  ('single_wall', 'no_wall' or 'in_plane' as given by `domain`, or 'free_surface': a rigid deck whose product is a
+  `<backend>_free_surface` one under `domain single_wall`, multi_bodies.py:262-265).
+
+  Above a free surface the dense blocks (uses_dense_blocks: the rigid schemes) may be `<backend>_no_wall` -- what a
+  reference deck can run: its `C++_free_surface` names a function mobility.py does not define -- or
+  `<backend>_free_surface`, this engine's own blocks (free_surface_blocks below).  The roller schemes do not run there:
+  the reference has no rotational products above a free surface."""
   domain = read.domain
   if domain not in ("single_wall", "no_wall", "in_plane"):
     raise ValueError("domain %r: expected single_wall, no_wall or in_plane" % (domain,))
+  # (a roller deck, uses_dense_blocks = False, raises here for a free-surface product)
   modes = [("mobility_vector_prod_implementation", hydrodynamic_mode(read.mobility_vector_prod_implementation,
-                                                                      "mobility_vector_prod_implementation"))]
+                                                                      "mobility_vector_prod_implementation", uses_dense_blocks))]
   if uses_dense_blocks:
     modes.append(("mobility_blobs_implementation", hydrodynamic_mode(read.mobility_blobs_implementation,
-                                                                     "mobility_blobs_implementation")))
+                                                                     "mobility_blobs_implementation", True)))
+    product, blocks = modes[0][1], modes[1][1]
+    if product != "free_surface" and blocks == "free_surface":
+      raise ValueError("mobility_blobs_implementation %r builds free surface blocks but mobility_vector_prod_implementation %r "
+                       "is a %s product: state the intended boundary"
+                       % (read.mobility_blobs_implementation, read.mobility_vector_prod_implementation, product))
+    if product == "free_surface":
+      if blocks == "single_wall":
+        raise ValueError("mobility_blobs_implementation %r builds wall blocks but mobility_vector_prod_implementation %r is a "
+                         "free surface product: use a <backend>_no_wall (the reference's choice) or <backend>_free_surface one"
+                         % (read.mobility_blobs_implementation, read.mobility_vector_prod_implementation))
+      if "dense_algebra" in read.scheme and blocks != "free_surface":
+        raise ValueError("scheme %s above a free surface takes the whole blob mobility from mobility_blobs_implementation: %r "
+                         "would run it unbounded; use a <backend>_free_surface one" % (read.scheme, read.mobility_blobs_implementation))
+      if domain != "single_wall":
+        raise ValueError("mobility_vector_prod_implementation %r (free surface) needs `domain single_wall` (the reference's "
+                         "position check), the deck says `domain %s`" % (read.mobility_vector_prod_implementation, domain))
+      modes = []
+      domain = "free_surface"
   want = "no_wall" if domain == "no_wall" else "single_wall"
   for option, mode in modes:
     if mode != want:
@@ -68,6 +96,11 @@ def validate(read, uses_dense_blocks=True):
     raise ValueError("body_body_force_torque_implementation %r: body-body forces (multi_bodies_functions.py:359-395, a Yukawa "
                      "potential between body centres) are not built; only `None`" % (bb,))
   return domain
+
+
+def free_surface_blocks(read):
+  """'no_wall' | 'free_surface': the dense blocks of a rigid deck that validate() found to run above a free surface."""
+  return hydrodynamic_mode(read.mobility_blobs_implementation, "mobility_blobs_implementation", True)
 
 
 def uniform_vertices(coor, blob_radius, path):

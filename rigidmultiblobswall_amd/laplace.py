@@ -174,6 +174,8 @@ class PhoreticSlip(object):
     bg = background_vector(background)
     self.c0, self.grad0 = float(bg[0]), t(bg[1:4])
     self.H = t(background_hessian(bg))
+    if getattr(susp, "boundary", None) == "free_surface":
+      raise ValueError("phoretic slip above a free surface: the Laplace layer operators have wall and unbounded images only")
     self.wall = bool(susp.wall if wall is None else wall)
     self.tolerance = float(tolerance)
     self.slip_body_frame = slip_body_frame

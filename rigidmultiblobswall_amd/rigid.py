@@ -103,12 +103,26 @@ class RigidSuspension(object):
   """
 
   def __init__(self, reference_configurations, locations, quaternions, a, eta, wall=True, periodic_length=None,
-               device="cuda:0", ctx=None, prescribed=None, prescribed_velocity=None):
-    """prescribed: optional bool per body -- bodies with prescribed kinematics (the reference's `obstacle` structures,
+               device="cuda:0", ctx=None, prescribed=None, prescribed_velocity=None, boundary=None, block_boundary=None):
+    """boundary: None (follow `wall`), "single_wall", "no_wall" or "free_surface" -- a stress-free surface at z = 0
+    (the reference's `numba_free_surface` / `pycuda_free_surface` products, multi_bodies.py:262-265): translational
+    blocks only, raw heights.  block_boundary: what the dense per-body blocks of the preconditioner (and
+    dense_blob_mobility) are built with above a free surface: "free_surface" (default: the blocks of the product) or
+    "no_wall" (what a reference deck with `mobility_blobs_implementation python_no_wall` runs).
+    prescribed: optional bool per body -- bodies with prescribed kinematics (the reference's `obstacle` structures,
     multi_bodies.py:1201-1203): their velocity is given (prescribed_velocity, default 0) and the unknown in their U slot
     is the force-torque that holds them (multi_bodies.py:457-462, :561-571)."""
     self.device = torch.device(device)
-    self.a, self.eta, self.wall = float(a), float(eta), bool(wall)
+    self.a, self.eta = float(a), float(eta)
+    if boundary is None:
+      boundary = "single_wall" if wall else "no_wall"
+    if boundary not in ("single_wall", "no_wall", "free_surface"):
+      raise ValueError("boundary must be single_wall, no_wall or free_surface")
+    self.boundary = boundary
+    self.free_surface = boundary == "free_surface"
+    self.block_boundary = boundary if block_boundary is None else block_boundary
+    if self.block_boundary != boundary and not (self.free_surface and self.block_boundary == "no_wall"):
+      raise ValueError("block_boundary %r with boundary %r: only a free surface takes other blocks (no_wall)" % (block_boundary, boundary))
     self.L = np.zeros(3) if periodic_length is None else np.asarray(periodic_length, dtype=np.float64)
     refs = [np.asarray(c, dtype=np.float64).reshape(len(c), -1)[:, :3] for c in reference_configurations]
     self.n_bodies = len(refs)
@@ -119,6 +133,22 @@ class RigidSuspension(object):
     self.body_sizes = sizes
     self.ctx = ctx if ctx is not None else MobilityContext(self.device.index or 0)
     self._own_ctx = ctx is None
+    # what set_positions gets as `wall`, and the kind of the blob product.  A context that knows the boundary
+    # (MobilityContext) is told so: its dense blocks and its rigid-body solver calls then carry the image.  Any other
+    # (test stand-ins) sees raw heights without a wall and is asked for "tt_free": the generic path.
+    # `wall` stays a boolean (no-slip wall or not); `ctx_wall` is the value handed to the context.
+    self.wall = boundary == "single_wall"
+    self.ctx_wall = self.wall
+    self._tt = "tt"
+    if self.free_surface:
+      from .multi import MultiContext
+      from .distributed import ReplicatedContext
+      if isinstance(self.ctx, (MultiContext, ReplicatedContext)):
+        raise ValueError("rigid bodies above a free surface run on one plain MobilityContext; %s is not served"
+                         % type(self.ctx).__name__)
+      self._tt = "tt_free"
+      if getattr(self.ctx, "supports_free_surface", False):
+        self.ctx_wall = "free_surface"
     # groups of equal n_b
     self.groups = []
     for n_b in sorted(set(sizes.tolist())):
@@ -184,7 +214,7 @@ class RigidSuspension(object):
         g.K = torch.empty((self.n_bodies, 3 * g.n_b, 6), dtype=torch.float64, device=self.device)
       self._native_blocks().rigid_configuration_device(g.ref, self.location, self.orientation, self._r_buf, g.rel, g.K)
       self.r_dev = self._r_buf.view(-1)
-      self.ctx.set_positions(self.r_dev, self.a, self.L, self.wall)
+      self.ctx.set_positions(self.r_dev, self.a, self.L, self.ctx_wall)
       return
     r, rels = self.blob_positions_device(self.location, self.orientation)
     for g, rel in zip(self.groups, rels):
@@ -199,15 +229,32 @@ class RigidSuspension(object):
       K[:, :, 1, 3] = -rel[:, :, 2]; K[:, :, 1, 5] = rel[:, :, 0]
       K[:, :, 2, 3] = rel[:, :, 1];  K[:, :, 2, 4] = -rel[:, :, 0]
     self.r_dev = r.reshape(-1)
-    self.ctx.set_positions(self.r_dev, self.a, self.L, self.wall)
+    self.ctx.set_positions(self.r_dev, self.a, self.L, self.ctx_wall)
 
   # ---- dense operators of the whole suspension (the reference's "dense algebra" schemes and one-shot utilities) ----
   def dense_blob_mobility(self):
     """(3N, 3N) blob mobility at the bound configuration: body_dense_tt_kernel with the whole suspension as one "body"
     (the reference calls self.mobility_blobs(r_vectors, eta, a), multi_bodies.py:207-230), symmetrised."""
     first = torch.zeros(1, dtype=torch.int64, device=self.device)
-    M = self.ctx.body_mobility_dense_device(first, self.n_blobs, self.eta)[0]
+    M = self._dense_blocks(first, self.n_blobs)[0]
     return 0.5 * (M + M.t())
+
+  def _dense_blocks(self, first_blob, n_b):
+    """Dense blob mobility of every body listed in first_blob, with the boundary `block_boundary` names."""
+    if not self.free_surface:
+      return self.ctx.body_mobility_dense_device(first_blob, n_b, self.eta)
+    if self.block_boundary == "free_surface":
+      if self.ctx_wall != "free_surface":
+        raise ValueError("dense free surface blocks need a MobilityContext; %s has none" % type(self.ctx).__name__)
+      return self.ctx.body_mobility_dense_device(first_blob, n_b, self.eta)
+    # unbounded blocks next to the free-surface product: the same raw heights, loaded without the boundary
+    if self.ctx_wall != "free_surface":
+      return self.ctx.body_mobility_dense_device(first_blob, n_b, self.eta)
+    self.ctx.set_positions(self.r_dev, self.a, self.L, False)
+    try:
+      return self.ctx.body_mobility_dense_device(first_blob, n_b, self.eta)
+    finally:
+      self.ctx.set_positions(self.r_dev, self.a, self.L, self.ctx_wall)
 
   def dense_K(self):
     """(3N, 6 n_bodies) block-diagonal geometric matrix (multi_bodies.py:300-324)."""
@@ -265,7 +312,7 @@ class RigidSuspension(object):
   def mobility_times_lambda(self, lam):
     self.matvec_count += 1
     self.sweep_count += 1
-    return self.ctx.matvec_device("tt", lam.contiguous(), self.eta)
+    return self.ctx.matvec_device(self._tt, lam.contiguous(), self.eta)
 
   def mobility_times_lambdas(self, lams):
     """M applied to several blob vectors with as few passes over the pairs as possible: up to `lockstep_width` vectors
@@ -278,9 +325,10 @@ class RigidSuspension(object):
       chunk = lams[lo:lo + width]
       self.matvec_count += len(chunk)
       self.sweep_count += 1
-      if len(chunk) == 1 or not hasattr(self.ctx, "matvec_op_device"):
+      if len(chunk) == 1 or not hasattr(self.ctx, "matvec_op_device") or self.free_surface:
+        # (no fused multi-vector pass above a free surface: one sweep per vector)
         self.sweep_count += len(chunk) - 1
-        out.extend(self.ctx.matvec_device("tt", v, self.eta) for v in chunk)
+        out.extend(self.ctx.matvec_device(self._tt, v, self.eta) for v in chunk)
       else:
         if len(chunk) == 2:
           self.matvec2_count += 1
@@ -319,7 +367,7 @@ class RigidSuspension(object):
         # sweep + ONE finishing launch (self term, scaling, - K U, -K^T lambda): rmb_rigid_operator_device
         return helper.rigid_operator_device(g.K, x, self.eta, res)
       lam = lam.contiguous()
-      r = self.ctx.matvec_device("tt", lam, self.eta, out=top)
+      r = self.ctx.matvec_device(self._tt, lam, self.eta, out=top)
       if r.data_ptr() != top.data_ptr():       # contexts that do not write in place (test stand-ins)
         top.copy_(r)
       if self._native_products():
@@ -344,7 +392,7 @@ class RigidSuspension(object):
   def apply_operator2(self, xa, xb):
     """The operator applied to two vectors with ONE pass over the blob pairs (rmb_matvec2_device); the K products
     stay per vector (they are O(N)).  Falls back to two applications when the fast path does not apply."""
-    if self.free is not None or len(self.groups) != 1 or not hasattr(self.ctx, "matvec2_device"):
+    if self.free is not None or len(self.groups) != 1 or not hasattr(self.ctx, "matvec2_device") or self.free_surface:
       return self.apply_operator(xa), self.apply_operator(xb)
     n3 = 3 * self.n_blobs
     g = self.groups[0]
@@ -392,7 +440,7 @@ class RigidSuspension(object):
   def build_preconditioner(self):
     """Per body: M_b (dense, device kernel), Cholesky, N_b = (K^T M_b^-1 K)^-1 (multi_bodies.py:516-531)."""
     for g in self.groups:
-      Mb = self.ctx.body_mobility_dense_device(g.first_blob, g.n_b, self.eta)
+      Mb = self._dense_blocks(g.first_blob, g.n_b)
       if self._native_pc(g, Mb):
         continue
       Mb = 0.5 * (Mb + Mb.transpose(1, 2))
@@ -655,6 +703,8 @@ class RigidSuspension(object):
     fp64 and this is plain restarted GMRES.  Not used by default: `solve` is the reference's algorithm.
     Measured (2048 shells x 12 blobs, tol 1e-8, tools/experiments/exp_mixed_precision_solve.py): 15.8 ms against 18.5 ms -- 21 fp32
     sweeps + 3 fp64 ones instead of 19 fp64 sweeps; at this size the per-iteration host work limits the gain to 1.17x."""
+    if self.free_surface:
+      raise ValueError("solve_mixed_precision above a free surface: the single-precision products are not run there")
     if self.groups[0].Lchol is None:
       self.build_preconditioner()
     nrm = float(torch.linalg.norm(rhs))
@@ -839,7 +889,7 @@ class RigidSuspension(object):
       return self._blockdiag(self.mobility_times_lambda(self._blockdiag(w, "Linv", transpose=True)), "Linv")
 
     def two(u, v):
-      if not hasattr(self.ctx, "matvec2_device"):
+      if not hasattr(self.ctx, "matvec2_device") or self.free_surface:
         return one(u), one(v)
       self.matvec_count += 2
       self.matvec2_count += 1

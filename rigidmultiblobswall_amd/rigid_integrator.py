@@ -71,17 +71,20 @@ class RigidIntegrator(object):
 
   def __init__(self, reference_configurations, locations, quaternions, scheme, a, eta, tolerance=None,
                domain="single_wall", periodic_length=None, device="cuda:0", ctx=None, rng=None, seed=None,
-               prescribed=None, prescribed_velocity=None):
-    if domain not in ("single_wall", "no_wall"):
-      raise ValueError("domain must be single_wall or no_wall")
+               prescribed=None, prescribed_velocity=None, block_boundary=None):
+    """domain: "single_wall", "no_wall" or "free_surface" (a stress-free surface at z = 0: the reference's
+    `*_free_surface` products under `domain single_wall`; position check, wall repulsion and gravity as with the wall).
+    block_boundary: see RigidSuspension."""
+    if domain not in ("single_wall", "no_wall", "free_surface"):
+      raise ValueError("domain must be single_wall, no_wall or free_surface")
     self.device = torch.device(device)
     self.scheme = scheme
     self.a, self.eta = float(a), float(eta)
     self.domain = domain
     self.periodic_length = np.zeros(3) if periodic_length is None else np.asarray(periodic_length, dtype=np.float64)
-    self.susp = RigidSuspension(reference_configurations, locations, quaternions, a, eta, wall=(domain == "single_wall"),
+    self.susp = RigidSuspension(reference_configurations, locations, quaternions, a, eta, boundary=domain,
                                 periodic_length=self.periodic_length, device=device, ctx=ctx, prescribed=prescribed,
-                                prescribed_velocity=prescribed_velocity)
+                                prescribed_velocity=prescribed_velocity, block_boundary=block_boundary)
     self.location = self.susp.location.clone()
     self.orientation = self.susp.orientation.clone()
     self.Nblobs, self.Nbodies = self.susp.n_blobs, self.susp.n_bodies
@@ -167,6 +170,8 @@ class RigidIntegrator(object):
   def precision(self, value):
     if value not in ('single', 'double'):
       raise ValueError("precision must be 'single' or 'double'")
+    if value == 'single' and self.domain == "free_surface":
+      raise ValueError("precision = 'single' above a free surface: the rigid-body solves there run in double precision only")
     if value == 'single' and self.kT > 0.0 and self.scheme.startswith("stochastic"):
       # only the stochastic schemes form random finite differences (the per-step check covers later changes)
       from .rollers import _check_rfd_delta_for_single_precision
@@ -199,8 +204,9 @@ class RigidIntegrator(object):
     return location + U[:, 0:3] * dt, quaternion_multiply_torch(quaternion_from_rotation_torch(U[:, 3:6] * dt), orientation)
 
   def _valid(self, location, orientation):
-    """body.check_function (body/body.py:118-140): no blob below the wall plane."""
-    if self.domain != "single_wall":
+    """body.check_function (body/body.py:118-140): no blob below the wall plane (or the free surface: the reference runs
+    those decks under `domain single_wall`, quaternion_integrator_multi_bodies.py:1779)."""
+    if self.domain == "no_wall":
       return True
     r, _ = self.susp.blob_positions_device(location, orientation)
     if bool(torch.any(r[:, 2] < 0.0)):
@@ -235,7 +241,7 @@ class RigidIntegrator(object):
       if self.repulsion_strength != 0.0:
         helper.set_positions(r.view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
         f = helper.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a)
-        helper.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.wall)  # back to the mobility view
+        helper.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
       return helper.one_blob_force_device(r, self.a, self.g * self.blob_mass, self.repulsion_strength_wall, self.debye_length_wall,
                                           out=f).view(-1, 3)
     f = torch.zeros_like(r)
@@ -248,7 +254,7 @@ class RigidIntegrator(object):
       ctx = self.susp.ctx
       ctx.set_positions(r.contiguous().view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
       f = f + ctx.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a).view(-1, 3)
-      ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.wall)  # back to the mobility view
+      ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
     return f
 
   def force_torque_calculator(self):
@@ -816,16 +822,21 @@ def bodies_from_input(read):
 def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   """Integrator wired from a ReadInput deck as multi_bodies/multi_bodies.py:1319-1393 wires QuaternionIntegrator."""
   from . import deck_modes
-  deck_modes.validate(read, uses_dense_blocks=True)     # ValueError for modes this engine does not run
+  domain = deck_modes.validate(read, uses_dense_blocks=True)     # ValueError for modes this engine does not run
   phoretic = deck_modes.phoretic(read)                  # ValueError for phoretic modes this engine does not run
+  block_boundary = None
+  if domain == "free_surface":
+    if phoretic:
+      raise ValueError("phoretic deck above a free surface: the Laplace layer operators have wall and unbounded images only")
+    block_boundary = deck_modes.free_surface_blocks(read)
   b = bodies_from_input(read)
   refs, body_types, any_slip = b["refs"], b["body_types"], b["slips"] is not None
   if rng is None:
     rng = read.random_generator(save=False)
   rng = replicate_rng(rng, read, ctx, device)
   integ = RigidIntegrator(refs, b["locations"], b["quaternions"], read.scheme, read.blob_radius, read.eta,
-                          tolerance=read.solver_tolerance, domain=read.domain, periodic_length=read.periodic_length,
-                          device=device, ctx=ctx, rng=rng, prescribed=b["prescribed"])
+                          tolerance=read.solver_tolerance, domain=domain, periodic_length=read.periodic_length,
+                          device=device, ctx=ctx, rng=rng, prescribed=b["prescribed"], block_boundary=block_boundary)
   integ.kT = read.kT
   integ.rf_delta = read.rf_delta
   integ.update_PC = read.update_PC

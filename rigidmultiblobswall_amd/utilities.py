@@ -28,6 +28,13 @@ def _dense_K(rs):
   return rs.dense_K()
 
 
+def _boundary(read, impl):
+  """'single_wall' | 'no_wall' | 'free_surface' of a deck for the implementation string that decides the scheme's mobility."""
+  if read.domain == "no_wall" or "no_wall" in impl:
+    return "no_wall"
+  return "free_surface" if impl.endswith("_free_surface") and "radii" not in impl else "single_wall"
+
+
 def run(read, device="cuda:0", ctx=None, write=True):
   """Returns a dict with the arrays of the scheme (numpy) and writes the reference's output files."""
   scheme = read.scheme
@@ -35,13 +42,18 @@ def run(read, device="cuda:0", ctx=None, write=True):
     raise ValueError("scheme must be mobility, resistance or body_mobility (got %s)" % scheme)
   b = bodies_from_input(read)
   nb = len(b["refs"])
-  wall = read.domain != "no_wall" and "no_wall" not in read.mobility_blobs_implementation
-  if scheme == "mobility":
-    wall = read.domain != "no_wall" and "no_wall" not in read.mobility_vector_prod_implementation
+  # the deck's boundary: the dense schemes take their mobility from mobility_blobs_implementation, `mobility` from the product
+  boundary = _boundary(read, read.mobility_vector_prod_implementation if scheme == "mobility" else read.mobility_blobs_implementation)
   out = {}
   if scheme == "mobility":
+    block_boundary = None
+    if boundary == "free_surface":
+      block_boundary = _boundary(read, read.mobility_blobs_implementation)
+      if block_boundary == "single_wall":
+        raise ValueError("mobility_blobs_implementation %r builds wall blocks under a free surface product: use a "
+                         "<backend>_no_wall or <backend>_free_surface one" % (read.mobility_blobs_implementation,))
     integ = RigidIntegrator(b["refs"], b["locations"], b["quaternions"], "deterministic_forward_euler", read.blob_radius,
-                            read.eta, tolerance=read.solver_tolerance, domain="single_wall" if wall else "no_wall",
+                            read.eta, tolerance=read.solver_tolerance, domain=boundary, block_boundary=block_boundary,
                             periodic_length=read.periodic_length, device=device, ctx=ctx, prescribed=b["prescribed"])
     rs = integ.susp
     if b["slips"] is not None:
@@ -72,13 +84,14 @@ def run(read, device="cuda:0", ctx=None, write=True):
       grid = np.array(plot.split(), dtype=np.float64)
       tracer = float(read.options.get("tracer_radius") or 0.0)
       out["grid_coor"], out["grid_velocity"] = velocity_field(grid, rs.r_vectors, out["lambda_blobs"], read.blob_radius,
-                                                              read.eta, tracer, wall=wall,
+                                                              read.eta, tracer,
+                                                              wall="free_surface" if boundary == "free_surface" else boundary == "single_wall",
                                                               output=read.output_name if write else None)
     if ctx is None:
       integ.close()
     return out
 
-  rs = RigidSuspension(b["refs"], b["locations"], b["quaternions"], read.blob_radius, read.eta, wall=wall,
+  rs = RigidSuspension(b["refs"], b["locations"], b["quaternions"], read.blob_radius, read.eta, boundary=boundary,
                        device=device, ctx=ctx)
   M = _dense_blob_mobility(rs)
   K = _dense_K(rs)
@@ -113,7 +126,8 @@ def velocity_field(grid, r_vectors_blobs, lambda_blobs, blob_radius, eta, tracer
                    radius_blobs=None):
   """Fluid velocity on a rectilinear grid of tracers (multi_bodies_utilities.py:74-186).  grid = 9 numbers
   (x0 x1 nx  y0 y1 ny  z0 z1 nz); x is the fast axis.  Returns (grid_coor (n,3), velocity (n,3)); with `output`
-  also writes `<output>.velocity_field.vtk` (legacy VTK, rectilinear grid, cell data `velocity`)."""
+  also writes `<output>.velocity_field.vtk` (legacy VTK, rectilinear grid, cell data `velocity`).  wall: True, False or
+  "free_surface" (the image of a stress-free surface at z = 0)."""
   from . import mobility as mob
   grid = np.reshape(np.asarray(grid, dtype=np.float64), (3, 3)).T
   length = grid[1] - grid[0]
@@ -127,7 +141,8 @@ def velocity_field(grid, r_vectors_blobs, lambda_blobs, blob_radius, eta, tracer
   r = np.asarray(r_vectors_blobs, dtype=np.float64).reshape(-1, 3)
   radius_source = np.ones(len(r)) * blob_radius if radius_blobs is None else np.asarray(radius_blobs, dtype=np.float64)
   radius_target = np.ones(len(coor)) * tracer_radius
-  fn = (mob.single_wall_mobility_trans_times_force_source_target_hip if wall
+  fn = (mob.free_surface_mobility_trans_times_force_source_target_hip if wall == "free_surface"
+        else mob.single_wall_mobility_trans_times_force_source_target_hip if wall
         else mob.no_wall_mobility_trans_times_force_source_target_hip)
   vel = fn(r, coor, np.asarray(lambda_blobs, dtype=np.float64).reshape(-1), radius_source, radius_target, eta).reshape(-1, 3)
   if output is not None:

@@ -7,6 +7,8 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py                  this tree
   python tools/kernel_resources.py OTHER_TREE       OTHER_TREE | this tree, side by side, differing rows marked
   python tools/kernel_resources.py --potential      potential_kernel next to sym_force_kernel, every pair loop of each
+  python tools/kernel_resources.py --rigid [TREE]   the dense per-body blocks and the finishing launches of the rigid-body
+                                                    operator / Lanczos step (rmb_rigid.hip), every boundary instance
 """
 import os
 import re
@@ -25,14 +27,21 @@ def resident(vgpr, lds):
   return min(8, 512 // (8 * ((vgpr + 7) // 8)), (160 * 1024) // lds if lds else 8)
 
 
-def table(root):
+RIGID_UNITS = ("rmb_sweep.hip", "rmb_rigid.hip")
+RIGID_KERNELS = ("body_dense_tt_kernel", "rigid_operator_finish_kernel", "lanczos_finish_kernel", "plain_finish_kernel")
+
+
+def table(root, units=UNITS, only=None):
   rows = {}
-  for unit in UNITS:
+  for unit in units:
     asm = subprocess.run([isa_stats.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-S",
                           "--cuda-device-only", "-o", "-", os.path.join(root, "rigidmultiblobswall_amd", "csrc", unit)],
                          check=True, capture_output=True, text=True).stdout
     for m in INFO.finditer(asm):
+      if only is not None and not any(k in m.group(1) for k in only):
+        continue
       name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+      name = name.replace("(anonymous namespace)::", "")
       name = re.sub(r"\(.*", "", name).replace("void ", "")
       code, sgpr, vgpr, scratch, lds = (int(g) for g in m.groups()[1:])
       row = "vgpr %3d sgpr %3d scratch %d lds %5d res %d code %4d" % (vgpr, sgpr, scratch, lds, resident(vgpr, lds), code)
@@ -94,6 +103,11 @@ def potential_table(root):
 if __name__ == "__main__":
   if "--potential" in sys.argv:
     potential_table(isa_stats.ROOT)
+    sys.exit(0)
+  if "--rigid" in sys.argv:
+    root = sys.argv[sys.argv.index("--rigid") + 1] if len(sys.argv) > sys.argv.index("--rigid") + 1 else isa_stats.ROOT
+    for name, row in sorted(table(root, RIGID_UNITS, RIGID_KERNELS).items()):
+      print("%-72s %s" % (name.replace("rmbi::", "").replace("rmb::", ""), row))
     sys.exit(0)
   here = table(isa_stats.ROOT)
   other = table(sys.argv[1]) if len(sys.argv) > 1 else None
