@@ -27,6 +27,18 @@
  *     rmb_op but RMB_OP_TT_MULTI (one sweep per vector) return RMB_ERR_STATE: the reference has no
  *     rotational products above a free surface.  (An option, not wall == 2: every non-zero `wall` has
  *     always meant the no-slip wall here.)
+ *   - rotational products above a free surface, BEYOND the reference: with context option
+ *     "free_surface_rotation" = 1 (default 0: everything above stays as stated) a free-surface
+ *     configuration also serves RMB_TR / RMB_RT / RMB_RR / RMB_TT_TR, RMB_OP_VELOCITY_FROM_FORCE_TORQUE,
+ *     RMB_OP_GRAND, RMB_OP_FORCE_COLUMN, RMB_OP_{TR,RT,RR}_MULTI (one sweep per vector), their pair shards and
+ *     rmb_lanczos_device(product = grand).  The blocks are those of the mirror-image system of the unbounded
+ *     RPY tensors B_xx: the image of blob j sits at S r_j, S = diag(1, 1, -1); a force is a polar vector and
+ *     mirrors as S f, a torque is an axial one and mirrors as -S tau, so with R = (d_x, d_y, z_i + z_j)
+ *       M_tt = B_tt(d) + B_tt(R) S    M_tr = B_tr(d) - B_tr(R) S    M_rt = B_rt(d) + B_rt(R) S    M_rr = B_rr(d) - B_rr(R) S
+ *     (overlap patches included; i == j: the unbounded self term plus the blob's own image at R = (0, 0, 2 z_i)).
+ *     The 6N matrix is symmetric, and positive definite with open boundaries.  Double precision only
+ *     ("precision" = 32 with one of these products returns RMB_ERR_STATE), periodic_length[2] must be 0, no
+ *     in_plane variant, no two-vector pass: each refused with RMB_ERR_STATE, nothing else runs in their place.
  *   - every function returns 0 on success, a negative rmb_status otherwise; rmb_last_error()
  *     gives a message for the calling thread.  The reference defines no error codes (failures
  *     surface as Python exceptions from pycuda); the Python shim raises RuntimeError on non-zero.
@@ -113,6 +125,12 @@ int rmb_ctx_release_stream(rmb_ctx* ctx);
  *                          the source->target operators compute in fp64 whatever this says.  Other values:
  *                          RMB_ERR_ARG.  The "wave_clock" / "skip_pairs" diagnostics exist in the fp64 kernels only:
  *                          a product that would run an fp32 kernel with one of them set returns RMB_ERR_STATE.
+ *   "free_surface"    [0]  `wall` != 0 in the next rmb_set_positions* loads a configuration above a stress-free surface
+ *                          at z = 0 (conventions above)
+ *   "free_surface_rotation" [0]  1 = a free-surface configuration also serves the rotational blocks of the mirror-image
+ *                          system (a force mirrors as S f, a torque as -S tau; conventions above).  Beyond the reference;
+ *                          fp64 per-wave symmetric kernel from 128 blobs on, the one-sided sweep below / for target
+ *                          sub-ranges / "deterministic" = 1.  0 = those products return RMB_ERR_STATE
  *   "force_cull"      [1]  blob-blob forces (uniform radius, symmetric path; open or pseudo-periodic): skip tile pairs whose
  *                          bounding boxes are further apart than 2a + 750 b, where exp(-(r - 2a)/b) underflows to
  *                          exactly 0 in double precision (110 b for the float kernel): no bit of the result changes

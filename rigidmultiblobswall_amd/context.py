@@ -104,13 +104,16 @@ class MobilityContext(object):
     return int(v.value)
 
   supports_free_surface = True     # set_positions(wall="free_surface"), see there
+  supports_free_surface_rotation = True   # option "free_surface_rotation": tr / rt / rr / tt_tr and the multi-block operations there
 
   def set_positions(self, r_vectors, a, periodic_length=None, wall=True):
     """r_vectors: numpy (N,3)/(3N,) or a CUDA torch float64 tensor (stays on device).
     wall: True (no-slip wall at z = 0: clamped heights, B damping), False (unbounded) or "free_surface": a stress-free
     surface at z = 0 (context option "free_surface" + wall = 1 in the C ABI).  On such a configuration kind "tt" is the
     free-surface product and the dense blocks and the rigid-body solver calls carry its image; "tr" / "rt" / "rr" /
-    "tt_tr", in_plane and the multi-block operations raise (RMB_ERR_STATE)."""
+    "tt_tr", in_plane and the multi-block operations raise (RMB_ERR_STATE) -- the reference has no such products.
+    set_option("free_surface_rotation", 1) serves them from the mirror-image system (a force mirrors as S f, a torque
+    as -S tau, S = diag(1, 1, -1)): beyond the reference, fp64, periodic_length[2] = 0, no in_plane, no matvec2_device."""
     free_surface = isinstance(wall, str)
     if free_surface and wall != "free_surface":
       raise ValueError("wall must be True, False or \"free_surface\"")

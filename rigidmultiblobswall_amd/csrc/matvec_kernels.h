@@ -21,7 +21,7 @@ struct SweepArgs : OneSidedArgs {
   PairConsts k;
 };
 
-template <int KIND> struct Rec { static constexpr int n2 = (KIND == KIND_TT_TR) ? 5 : 3; };
+template <int KIND> struct Rec { static constexpr int n2 = kind_has_torque(KIND) ? 5 : 3; };
 
 template <int KIND, bool WALL, bool PERIODIC> struct SweepOp {
   typedef SweepArgs Args;
@@ -39,7 +39,7 @@ template <int KIND, bool WALL, bool PERIODIC> struct SweepOp {
     rec[0] = make_double2(p.x, p.y);
     rec[1] = make_double2(p.z, vx);
     rec[2] = make_double2(vy, vz);
-    if constexpr (KIND == KIND_TT_TR) {
+    if constexpr (kind_has_torque(KIND)) {
       double wx = a.vec2[3 * j] * b, wy = a.vec2[3 * j + 1] * b, wz = a.vec2[3 * j + 2] * b;
       if (a.in_plane) wz = 0.0;
       rec[3] = make_double2(wx, wy);
@@ -57,7 +57,7 @@ template <int KIND, bool WALL, bool PERIODIC> struct SweepOp {
       const double2 q1 = tile[s * REC2 + 1];
       const double2 q2 = tile[s * REC2 + 2];
       double wx = 0, wy = 0, wz = 0;
-      if constexpr (KIND == KIND_TT_TR) {
+      if constexpr (kind_has_torque(KIND)) {
         const double2 q3 = tile[s * REC2 + 3];
         const double2 q4 = tile[s * REC2 + 4];
         wx = q3.x; wy = q3.y; wz = q4.x;
@@ -87,9 +87,9 @@ template <int KIND, bool WALL, bool PERIODIC> struct SweepOp {
     const double b = tp.w;
     double vx = a.vec[3 * ti] * b, vy = a.vec[3 * ti + 1] * b, vz = a.vec[3 * ti + 2] * b;
     double wx = 0, wy = 0, wz = 0;
-    if constexpr (KIND == KIND_TT_TR) { wx = a.vec2[3 * ti] * b; wy = a.vec2[3 * ti + 1] * b; wz = a.vec2[3 * ti + 2] * b; }
+    if constexpr (kind_has_torque(KIND)) { wx = a.vec2[3 * ti] * b; wy = a.vec2[3 * ti + 1] * b; wz = a.vec2[3 * ti + 2] * b; }
     if (a.in_plane) { vz = 0.0; wz = 0.0; }
-    self_term<KIND, WALL>(a.k, tp.z, vx, vy, vz, wx, wy, wz, acc);
+    kind_self_term<KIND, WALL>(a.k, tp.z, vx, vy, vz, wx, wy, wz, acc);
     const double sc = a.prefactor * b;
     const long o = 3 * (ti - a.tgt_begin);
     a.out[o] = acc.x * sc; a.out[o + 1] = acc.y * sc; a.out[o + 2] = a.in_plane ? 0.0 : acc.z * sc;

@@ -364,6 +364,128 @@ __device__ __forceinline__ void pair_tt_forward(const PairConsts& k, double dx, 
   u.x = u3[0]; u.y = u3[1]; u.z = u3[2];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Free (stress-free) surface at z = 0: all four blocks from the mirror-image system of the unbounded tensors.
+// The image of blob j sits at S r_j, S = diag(1, 1, -1), so target i sees it at R = (d_x, d_y, z_i + z_j).  A force is
+// a polar vector -- its image is S f -- and a torque an axial one -- its image is -S tau:
+//   M_tt = B_tt(d) + B_tt(R) S     M_tr = B_tr(d) - B_tr(R) S     M_rt = B_rt(d) + B_rt(R) S     M_rr = B_rr(d) - B_rr(R) S
+// with B_xx the unbounded RPY blocks above, overlap patches included (tt is the reference's product,
+// mobility_numba.py:1840-1926; the rotational blocks go beyond the reference, which has none above this boundary).
+// The reversed pair sees R' = (-d_x, -d_y, R_z) = -S R.  For the even blocks (tt, rr: F I + P R R^T)
+// B(R') S = S B(R), for the couplings (c [. x R]) (S v) x R' = S (v x R): both directions come from one set of
+// coefficients, as the 6N matrix is symmetric.  Raw heights (no clamp, no damping).
+// ---------------------------------------------------------------------------------------------
+
+// the image separation as a geometry of its own: d_z -> R_z, 1/r -> 1/|R|  (g from make_geom<true>)
+__device__ __forceinline__ Geom image_geom(const Geom& g) {
+  Geom h;
+  h.dx = g.dx; h.dy = g.dy; h.dz = g.Rz;
+  h.rho2 = g.rho2;
+  h.r2 = __builtin_fma(g.Rz, g.Rz, g.rho2);
+  h.ir = g.iR; h.ir2 = g.iR2;
+  h.Rz = 0.0; h.iR = 0.0; h.iR2 = 0.0;
+  return h;
+}
+
+// even block (tt: SIGN = +1, rr: SIGN = -1) at the image separation h:  ui += SIGN B(R) S vj ;  t += SIGN S B(R) vi
+template <int SIGN>
+__device__ __forceinline__ void image_even_apply(const BlockM& m, const Geom& h, const double* vi, const double* vj, double* ui, double* t) {
+  BlockM c = m;
+  if constexpr (SIGN < 0) { c.F = -m.F; c.P = -m.P; }
+  const double vjs[3] = {vj[0], vj[1], -vj[2]};
+  double ts[3] = {t[0], t[1], -t[2]};
+  tt_apply<false, true>(c, h, vi, vjs, ui, ts);
+  t[0] = ts[0]; t[1] = ts[1]; t[2] = -ts[2];
+}
+
+// coupling block (rt: SIGN = +1, tr: SIGN = -1) at the image separation:  ui += SIGN c (S vj) x R ;  t += SIGN c S (vi x R)
+template <int SIGN>
+__device__ __forceinline__ void image_coupling_apply(double c, const Geom& h, const double* vi, const double* vj, double* ui, double* t) {
+  const double vjs[3] = {vj[0], vj[1], -vj[2]};
+  double ts[3] = {-t[0], -t[1], t[2]};          // coupling_rpy_apply adds -c (vi x R):  t = -S ts
+  coupling_rpy_apply<true>(SIGN < 0 ? -c : c, h, vi, vjs, ui, ts);
+  t[0] = -ts[0]; t[1] = -ts[1]; t[2] = ts[2];
+}
+
+// The blocks TT / TR / RT / RR of one pair, both directions: two geometries and two coefficient sets shared by all of them.
+//   (fi, fj) forces, (ti, tj) torques of the two blobs;  u / w += velocity / angular velocity of blob i,
+//   tu / tw (+)= those of blob j (ACC as above).  Pointers of blocks that are not asked for are never touched.
+template <bool TT, bool TR, bool RT, bool RR, bool ACC>
+__device__ __forceinline__ void free_surface_pair(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
+                                                  const double* fi, const double* fj, const double* ti, const double* tj,
+                                                  double* u, double* w, double* tu, double* tw) {
+  if constexpr (!ACC) {
+    if constexpr (TT || TR) { tu[0] = 0.0; tu[1] = 0.0; tu[2] = 0.0; }
+    if constexpr (RT || RR) { tw[0] = 0.0; tw[1] = 0.0; tw[2] = 0.0; }
+  }
+  const Geom g = make_geom<true>(dx, dy, dz, zi, zj);
+  const Geom h = image_geom(g);
+  const Rpy p = rpy_coeffs<TT, TR || RT, RR>(k, g);
+  const Rpy q = rpy_coeffs<TT, TR || RT, RR>(k, h);
+  if constexpr (TT) {
+    tt_apply<false, true>(tt_block<false>(k, g, zi, zj, p.cF, p.cD), g, fi, fj, u, tu);
+    image_even_apply<1>(tt_block<false>(k, h, zi, zj, q.cF, q.cD), h, fi, fj, u, tu);
+  }
+  if constexpr (TR) {
+    tr_apply<false, true>(cpl_block<false>(k, g, zi, zj, p.c), g, ti, tj, u, tu);
+    image_coupling_apply<-1>(q.c, h, ti, tj, u, tu);
+  }
+  if constexpr (RT) {
+    rt_apply<false, true>(cpl_block<false>(k, g, zi, zj, p.c), g, fi, fj, w, tw);
+    image_coupling_apply<1>(q.c, h, fi, fj, w, tw);
+  }
+  if constexpr (RR) {
+    rr_apply<false, true>(rr_block<false>(k, g, p.rF, p.rD), g, ti, tj, w, tw);
+    image_even_apply<-1>(rr_block<false>(k, h, q.rF, q.rD), h, ti, tj, w, tw);
+  }
+}
+
+// i == j: the unbounded self term (tt: 4/(3a), rr: 1/a^3, couplings: none) plus the blob's own image, the pair formula at
+// R = (0, 0, 2 z_i) in the forward direction (as self_term<KIND_TT_FREE> for tt alone)
+template <bool TT, bool TR, bool RT, bool RR>
+__device__ __forceinline__ void free_surface_self(const PairConsts& k, double zi, const double* f, const double* tau, double* u, double* w) {
+  const Geom h = make_geom<false>(0.0, 0.0, zi + zi, zi, zi);
+  const Rpy q = rpy_coeffs<TT, TR || RT, RR>(k, h);
+  const double none[3] = {0.0, 0.0, 0.0};
+  double t[3] = {0.0, 0.0, 0.0};                 // the reversed direction is dead code here
+  if constexpr (TT) {
+    u[0] = __builtin_fma(k.tt_n0, f[0], u[0]); u[1] = __builtin_fma(k.tt_n0, f[1], u[1]); u[2] = __builtin_fma(k.tt_n0, f[2], u[2]);
+    image_even_apply<1>(tt_block<false>(k, h, zi, zi, q.cF, q.cD), h, none, f, u, t);
+  }
+  if constexpr (TR) image_coupling_apply<-1>(q.c, h, none, tau, u, t);
+  if constexpr (RT) image_coupling_apply<1>(q.c, h, none, f, w, t);
+  if constexpr (RR) {
+    w[0] = __builtin_fma(k.rr_m0, tau[0], w[0]); w[1] = __builtin_fma(k.rr_m0, tau[1], w[1]); w[2] = __builtin_fma(k.rr_m0, tau[2], w[2]);
+    image_even_apply<-1>(rr_block<false>(k, h, q.rF, q.rD), h, none, tau, w, t);
+  }
+}
+
+// one-sided forms of the rotational free-surface kinds: (v) the source vector, (w) the torque of KIND_TT_TR_FREE; vi = 0 and the
+// reversed direction are dead code
+template <int KIND, bool SELF>
+__device__ __forceinline__ void free_surface_forward(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
+                                                     double vx, double vy, double vz, double wx, double wy, double wz, Vec3& u) {
+  const double none[3] = {0.0, 0.0, 0.0}, v[3] = {vx, vy, vz}, w[3] = {wx, wy, wz};
+  double o[3] = {u.x, u.y, u.z}, t[3];
+  if constexpr (KIND == KIND_TR_FREE) {
+    if constexpr (SELF) free_surface_self<false, true, false, false>(k, zi, nullptr, v, o, nullptr);
+    else free_surface_pair<false, true, false, false, false>(k, dx, dy, dz, zi, zj, nullptr, nullptr, none, v, o, nullptr, t, nullptr);
+  }
+  if constexpr (KIND == KIND_RT_FREE) {
+    if constexpr (SELF) free_surface_self<false, false, true, false>(k, zi, v, nullptr, nullptr, o);
+    else free_surface_pair<false, false, true, false, false>(k, dx, dy, dz, zi, zj, none, v, nullptr, nullptr, nullptr, o, nullptr, t);
+  }
+  if constexpr (KIND == KIND_RR_FREE) {
+    if constexpr (SELF) free_surface_self<false, false, false, true>(k, zi, nullptr, v, nullptr, o);
+    else free_surface_pair<false, false, false, true, false>(k, dx, dy, dz, zi, zj, nullptr, nullptr, none, v, nullptr, o, nullptr, t);
+  }
+  if constexpr (KIND == KIND_TT_TR_FREE) {
+    if constexpr (SELF) free_surface_self<true, true, false, false>(k, zi, v, w, o, nullptr);
+    else free_surface_pair<true, true, false, false, false>(k, dx, dy, dz, zi, zj, none, v, none, w, o, nullptr, t, nullptr);
+  }
+  u.x = o[0]; u.y = o[1]; u.z = o[2];
+}
+
 template <int KIND, bool WALL>
 __device__ __forceinline__ void pair_apply(const PairConsts& k, double dx, double dy, double dz, double zi,
                                            double zj, double vx, double vy, double vz, double wx, double wy,
@@ -383,6 +505,15 @@ __device__ __forceinline__ void pair_apply(const PairConsts& k, double dx, doubl
     pair_tt<false>(k, dx, dy, dz, Rz, zj, vx, vy, vz, u);
     pair_tt<false>(k, dx, dy, Rz, Rz, zj, vx, vy, -vz, u);
   }
+  if constexpr (KIND > KIND_TT_FREE) free_surface_forward<KIND, false>(k, dx, dy, dz, zi, zj, vx, vy, vz, wx, wy, wz, u);
+}
+
+// the i == j term of kind KIND (self_term of pair_ops.h; the rotational free-surface kinds carry the blob's own image)
+template <int KIND, bool WALL>
+__device__ __forceinline__ void kind_self_term(const PairConsts& k, double zi, double vx, double vy, double vz, double wx, double wy,
+                                               double wz, Vec3& u) {
+  if constexpr (KIND > KIND_TT_FREE) free_surface_forward<KIND, true>(k, 0.0, 0.0, 0.0, zi, zi, vx, vy, vz, wx, wy, wz, u);
+  else self_term<KIND, WALL>(k, zi, vx, vy, vz, wx, wy, wz, u);
 }
 
 }  // namespace rmb

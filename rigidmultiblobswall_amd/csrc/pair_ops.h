@@ -33,7 +33,13 @@ constexpr int kBlock = 64 * kWaves;
 constexpr int kSymWaves = 4;         // symmetric kernels (sym*_kernels.h)
 constexpr int kSymWavesPerEu = 4;    // register budget of sym_kernel / sym2_kernel: 4 waves per SIMD (the launch plan relies on it)
 
-enum Kind : int { KIND_TT = 0, KIND_TR = 1, KIND_RT = 2, KIND_RR = 3, KIND_TT_TR = 4, KIND_TT_FREE = 5, KIND_COUNT = 6 };
+enum Kind : int { KIND_TT = 0, KIND_TR = 1, KIND_RT = 2, KIND_RR = 3, KIND_TT_TR = 4, KIND_TT_FREE = 5,
+                  // rotational products above a free surface (context option "free_surface_rotation"; internal: the entry points
+                  // map RMB_TR / RT / RR / TT_TR of a free-surface context onto them, callers pass 0..5)
+                  KIND_TR_FREE = 6, KIND_RT_FREE = 7, KIND_RR_FREE = 8, KIND_TT_TR_FREE = 9, KIND_COUNT = 10 };
+constexpr int kPublicKinds = KIND_TT_FREE + 1;      // the kinds of include/rmb_mobility.h
+// kinds whose source carries a second vector (the torque next to the force)
+constexpr bool kind_has_torque(int kind) { return kind == KIND_TT_TR || kind == KIND_TT_TR_FREE; }
 
 // Uniform constants (host-computed from the blob radius a; see make_pair_consts in rmb_plan.hip).
 struct PairConsts {

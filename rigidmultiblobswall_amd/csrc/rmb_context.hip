@@ -187,6 +187,8 @@ int rmb_ctx_set_option(rmb_ctx* c, const char* key, long value) {
   if (!strcmp(key, "sym_pin")) { c->opt_sym_pin = value; return 0; }
   // takes effect at the next rmb_set_positions*: wall != 0 then loads a configuration above a stress-free surface
   if (!strcmp(key, "free_surface")) { c->opt_free_surface = value ? 1 : 0; return 0; }
+  // takes effect at the next product: a free-surface configuration serves the rotational blocks of the mirror-image system
+  if (!strcmp(key, "free_surface_rotation")) { c->opt_free_surface_rotation = value ? 1 : 0; return 0; }
   if (!strcmp(key, "precision")) {
     if (value != 32 && value != 64) return fail(RMB_ERR_ARG, "precision must be 32 or 64");
     c->opt_precision = value;
@@ -228,6 +230,7 @@ int rmb_ctx_get_option(rmb_ctx* c, const char* key, long* value) {
       {"fused_symmetric", &c->opt_fused_symmetric}, {"symx_single", &c->opt_symx_single},
       {"deterministic", &c->opt_deterministic}, {"det_workspace_mb", &c->opt_det_workspace_mb}, {"sym_wps", &c->opt_sym_wps},
       {"wave_clock", &c->opt_wave_clock}, {"skip_pairs", &c->opt_skip_pairs}, {"sym_pin", &c->opt_sym_pin}, {"free_surface", &c->opt_free_surface},
+      {"free_surface_rotation", &c->opt_free_surface_rotation},
       {"precision", &c->opt_precision}, {"force_precision", &c->opt_force_precision}, {"force_cull", &c->opt_force_cull}, {"force_sort", &c->opt_force_sort}, {"potential_resort", &c->opt_potential_resort}, {"sym_oversub", &c->opt_sym_oversub}, {"sym_fine_steps", &c->opt_sym_fine_steps}, {"sym_coop", &c->opt_sym_coop}, {"sym_order", &c->opt_sym_order}, {"host_zero_copy", &c->opt_host_zero_copy}, {"host_zero_copy_in", &c->opt_host_zero_copy_in}, {"gmres_fuse_pc", &c->opt_gmres_fuse_pc}, {"gmres_fuse_dots", &c->opt_gmres_fuse_dots}, {"krylov_low_sync", &c->opt_krylov_low_sync}, {"lanczos_fuse_finish", &c->opt_lanczos_fuse_finish}, {"sym_two_targets", &c->opt_sym_two_targets}, {"sym_chunk_steps", &c->opt_sym_chunk_steps}, {"sym_xcd", &c->opt_sym_xcd},
       {"sym_min_steps", &c->opt_sym_min_steps}};
   // read-only: which kernel family the last product ran on (0 one-sided sweep, 1 symmetric per-wave, 2 deterministic

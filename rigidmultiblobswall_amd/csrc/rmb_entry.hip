@@ -9,30 +9,56 @@
 namespace rmbi {
 
 namespace {
-// On a free-surface context RMB_TT is the free-surface product; nothing else exists above that boundary (the reference has
-// no rotational products there: mobility_numba.py has free_surface_mobility_trans_times_force only)
-int free_surface_kind(int* kind, int in_plane) {
-  if (*kind != rmb::KIND_TT && *kind != rmb::KIND_TT_FREE)
-    return fail(RMB_ERR_STATE, "free-surface context: only RMB_TT exists above a free surface (no tr / rt / rr / tt_tr products)");
+// What the rotational products above a free surface (option "free_surface_rotation") do not have: an in-plane variant, the
+// fp32 twins, pseudo-periodic images along z.  Refused by name -- a missing variant must not run something else.
+int free_surface_rotation_ok(const rmb_ctx* c, int in_plane) {
+  if (in_plane) return fail(RMB_ERR_STATE, "free-surface context: in_plane products are not served above a free surface here (load the configuration with wall = 0 and use RMB_TT_FREE_SURFACE)");
+  if (c->opt_precision == 32) return fail(RMB_ERR_STATE, "free-surface context: the rotational products above a free surface are double precision only (set \"precision\" = 64)");
+  if (c->L[2] > 0) return fail(RMB_ERR_STATE, "free-surface context: the rotational products above a free surface take periodic_length[2] = 0 (images in x and y only)");
+  return 0;
+}
+
+// On a free-surface context RMB_TT is the free-surface product, and nothing else exists above that boundary in the reference
+// (mobility_numba.py has free_surface_mobility_trans_times_force only).  With option "free_surface_rotation" RMB_TR / RT / RR /
+// TT_TR are the blocks of the mirror-image system (pair_blocks.h, free_surface_pair): internal kinds KIND_*_FREE.
+int free_surface_kind(const rmb_ctx* c, int* kind, int in_plane) {
+  if (*kind != rmb::KIND_TT && *kind != rmb::KIND_TT_FREE) {
+    if (!c->opt_free_surface_rotation)
+      return fail(RMB_ERR_STATE, "free-surface context: only RMB_TT exists above a free surface (no tr / rt / rr / tt_tr products)");
+    if (int rc = free_surface_rotation_ok(c, in_plane)) return rc;
+    *kind = *kind == rmb::KIND_TT_TR ? rmb::KIND_TT_TR_FREE : rmb::KIND_TR_FREE + (*kind - rmb::KIND_TR);
+    return 0;
+  }
   if (in_plane) return fail(RMB_ERR_STATE, "free-surface context: in_plane products are not served above a free surface here (load the configuration with wall = 0 and use RMB_TT_FREE_SURFACE)");
   *kind = rmb::KIND_TT_FREE;
   return 0;
+}
+
+// the generic symmetric operation of a free-surface kind
+int free_surface_sx(int kind) {
+  switch (kind) {
+    case rmb::KIND_TR_FREE: return SX_FREE_TR;
+    case rmb::KIND_RT_FREE: return SX_FREE_RT;
+    case rmb::KIND_RR_FREE: return SX_FREE_RR;
+    case rmb::KIND_TT_TR_FREE: return SX_FREE_FUSED;
+    default: return SX_FREE;
+  }
 }
 }  // namespace
 
 int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, const double* v2, double eta,
                        double* out) {
   if (int rc = check_ready(c)) return rc;
-  if (kind < 0 || kind >= rmb::KIND_COUNT) return fail(RMB_ERR_ARG, "kind must be 0..5");
+  if (kind < 0 || kind >= rmb::kPublicKinds) return fail(RMB_ERR_ARG, "kind must be 0..5");
   if (c->free_surface) {
-    if (int rc = free_surface_kind(&kind, in_plane)) return rc;
+    if (int rc = free_surface_kind(c, &kind, in_plane)) return rc;
   }
   if (kind == rmb::KIND_TT_FREE && c->wall)
     return fail(RMB_ERR_STATE, "RMB_TT_FREE_SURFACE uses raw heights: call rmb_set_positions with wall = 0");
   const long n_tgt = c->tgt_end - c->tgt_begin;
   if (n_tgt == 0) return 0;
   if (!v || !out) return fail(RMB_ERR_ARG, "null vector / output pointer");
-  if (kind == rmb::KIND_TT_TR && !v2) return fail(RMB_ERR_ARG, "RMB_TT_TR needs vec2 (torque)");
+  if (rmb::kind_has_torque(kind) && !v2) return fail(RMB_ERR_ARG, "RMB_TT_TR needs vec2 (torque)");
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   RMB_HIP(hipSetDevice(c->device));
 
@@ -44,7 +70,7 @@ int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, cons
     const double* in[2] = {v, v2};
     double* outs[1] = {out};
     if (c->opt_deterministic == 2) {   // bit-reproducible AND symmetric: ordered reduction instead of atomics
-      const int sx = kind <= rmb::KIND_RR ? SX_TT + kind : (kind == rmb::KIND_TT_TR ? SX_FUSED : SX_FREE);
+      const int sx = kind <= rmb::KIND_RR ? SX_TT + kind : (kind == rmb::KIND_TT_TR ? SX_FUSED : free_surface_sx(kind));
       return symx_det_device(c, sx, in, outs, eta, in_plane);
     }
     if (kind <= rmb::KIND_RR) {
@@ -61,7 +87,7 @@ int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, cons
       }
       if (c->opt_fused_symmetric) return symx_device(c, SX_FUSED, in, outs, eta, in_plane, 0, 1);
     }
-    if (kind == rmb::KIND_TT_FREE) return symx_device(c, SX_FREE, in, outs, eta, in_plane, 0, 1);
+    if (kind >= rmb::KIND_TT_FREE) return symx_device(c, free_surface_sx(kind), in, outs, eta, in_plane, 0, 1);
     c->last_path = 0;
   }
   return sweep_device(c, kind, in_plane, v, v2, eta, out);
@@ -94,10 +120,13 @@ int force_device_impl(rmb_ctx* c, double eps, double b, double blob_radius, doub
 // kinds with in_plane go through matvec_op_impl's *_MULTI operations); the public rmb_matvec_pairshard_device passes 0.
 int matvec_pairshard_impl(rmb_ctx* c, int kind, int in_plane, const double* v, double eta, double* out, long shard, long nshards) {
   if (int rc = check_ready(c)) return rc;
-  if (c->free_surface && kind >= 0 && kind < rmb::KIND_COUNT) {
-    if (int rc = free_surface_kind(&kind, in_plane)) return rc;
+  if (c->free_surface && kind >= 0 && kind < rmb::kPublicKinds) {
+    if (int rc = free_surface_kind(c, &kind, in_plane)) return rc;
+  } else if (kind >= rmb::kPublicKinds) {
+    kind = -1;      // the internal kinds are not a caller's to pass
   }
-  if ((kind < 0 || kind > rmb::KIND_RR) && kind != rmb::KIND_TT_FREE)
+  const bool free_kind = kind == rmb::KIND_TT_FREE || (kind >= rmb::KIND_TR_FREE && kind <= rmb::KIND_RR_FREE);
+  if ((kind < 0 || kind > rmb::KIND_RR) && !free_kind)
     return fail(RMB_ERR_ARG, "pair sharding is implemented for RMB_TT / TR / RT / RR / TT_FREE_SURFACE (RMB_TT_TR: rmb_matvec_op_pairshard_device)");
   if (kind == rmb::KIND_TT_FREE && c->wall)
     return fail(RMB_ERR_STATE, "RMB_TT_FREE_SURFACE uses raw heights: call rmb_set_positions with wall = 0");
@@ -109,12 +138,12 @@ int matvec_pairshard_impl(rmb_ctx* c, int kind, int in_plane, const double* v, d
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   RMB_HIP(hipSetDevice(c->device));
   c->last_path = 1;
-  const int sx = kind == rmb::KIND_TT_FREE ? SX_FREE : SX_TT + kind;
+  const int sx = free_kind ? free_surface_sx(kind) : SX_TT + kind;
   const double* in[2] = {v, nullptr};
   double* outs[1] = {out};
   if (c->opt_deterministic == 2)        // bit-reproducible shard: whole units, ordered reduction (symx_det_device)
     return symx_det_device(c, sx, in, outs, eta, in_plane ? 1 : 0, shard, nshards);
-  if (kind == rmb::KIND_TT_FREE) return symx_device(c, SX_FREE, in, outs, eta, in_plane ? 1 : 0, shard, nshards);
+  if (free_kind) return symx_device(c, sx, in, outs, eta, in_plane ? 1 : 0, shard, nshards);
   return sym_device(c, kind, v, eta, out, shard, nshards);
 }
 
@@ -144,13 +173,19 @@ int matvec_op_impl(rmb_ctx* c, int op, int in_plane, int n_in, const double* con
   if (c->n == 0) return 0;
   RMB_HIP(hipSetDevice(c->device));
   if (c->free_surface) {
-    // no fused multi-vector pass above a free surface: RMB_OP_TT_MULTI is one free-surface sweep per vector, the other
-    // operations need rotational blocks the boundary does not have
-    if (op != RMB_OP_TT_MULTI) return fail(RMB_ERR_STATE, "free-surface context: only RMB_OP_TT_MULTI is served (one sweep per vector); no rotational blocks above a free surface");
-    for (int v = 0; v < n_in; ++v)
-      if (int rc = nshards > 1 ? matvec_pairshard_impl(c, rmb::KIND_TT, in_plane, in[v], eta, out[v], shard, nshards)
-                               : matvec_device_impl(c, rmb::KIND_TT, in_plane, in[v], nullptr, eta, out[v])) return rc;
-    return 0;
+    // no fused multi-vector pass above a free surface: RMB_OP_*_MULTI is one free-surface sweep per vector; the other
+    // operations need rotational blocks the reference's boundary does not have (option "free_surface_rotation")
+    if (op != RMB_OP_TT_MULTI && !c->opt_free_surface_rotation) return fail(RMB_ERR_STATE, "free-surface context: only RMB_OP_TT_MULTI is served (one sweep per vector); no rotational blocks above a free surface");
+    if (op >= RMB_OP_TT_MULTI && op <= RMB_OP_RR_MULTI) {
+      for (int v = 0; v < n_in; ++v)
+        if (int rc = nshards > 1 ? matvec_pairshard_impl(c, multi_kind, in_plane, in[v], eta, out[v], shard, nshards)
+                                 : matvec_device_impl(c, multi_kind, in_plane, in[v], nullptr, eta, out[v])) return rc;
+      return 0;
+    }
+    // fused row, grand mobility, force column of the mirror-image system: routed below like their wall twins (the one-sided
+    // composition maps its kinds in matvec_device_impl)
+    if (int rc = free_surface_rotation_ok(c, in_plane)) return rc;
+    sx = op == RMB_OP_GRAND ? SX_FREE_GRAND : (op == RMB_OP_FORCE_COLUMN ? SX_FREE_COLF : SX_FREE_FUSED);
   }
   // a pair shard always writes all n targets, whatever target range is set (as rmb_matvec_pairshard_device)
   if (c->opt_deterministic == 2 && (nshards > 1 || sym_applies(c))) return symx_det_device(c, sx, in, out, eta, in_plane, shard, nshards);

@@ -72,6 +72,8 @@ struct rmb_ctx {
   int free_surface = 0;          // the configuration was loaded with wall != 0 under option "free_surface": raw heights (wall = 0 above),
                                  // kind tt is the free-surface product
   long opt_free_surface = 0;     // rmb_set_positions*(wall != 0) means a stress-free surface at z = 0, not a no-slip wall
+  long opt_free_surface_rotation = 0;   // a free-surface configuration also serves tr / rt / rr / tt_tr and the multi-block operations
+                                        // (mirror-image blocks beyond the reference; 0: refused, as the reference has none)
   bool have_positions = false;
   long tgt_begin = 0, tgt_end = 0;
   // device memory
@@ -268,7 +270,9 @@ inline double inv_length(double L) { return L > 0 ? 1.0 / L : 0.0; }   // recipr
 
 // ---- rmb_sym.hip -------------------------------------------------------------------------------------------
 // SX_K2 + 4 (k - 2) + kind: one block on k = 2..4 vectors
-enum SymXOp { SX_TT = 0, SX_TR, SX_RT, SX_RR, SX_FUSED, SX_GRAND, SX_COLF, SX_FREE, SX_RADII, SX_K2, SX_COUNT = SX_K2 + 12 };
+// SX_FREE_*: the rotational products above a free surface (option "free_surface_rotation"): per-wave fp64 kernel only
+enum SymXOp { SX_TT = 0, SX_TR, SX_RT, SX_RR, SX_FUSED, SX_GRAND, SX_COLF, SX_FREE, SX_RADII,
+              SX_FREE_TR, SX_FREE_RT, SX_FREE_RR, SX_FREE_FUSED, SX_FREE_GRAND, SX_FREE_COLF, SX_K2, SX_COUNT = SX_K2 + 12 };
 // Configuration a symmetric pass runs on: the context's resident one, or a caller-packed one (per-blob radii)
 struct SymConf { const double4* pos; long n; double L[3]; int wall; const double* extra; };
 template <class A, class = void> struct HasNPad : std::false_type {};

@@ -485,7 +485,7 @@ int run_host(rmb_multi* m, const Product& p, const double* const* in_host, doubl
 }
 
 int product_of_kind(rmb_multi* m, int kind, int in_plane, bool have_vec2, double eta, Product* p) {
-  if (kind < 0 || kind >= rmb::KIND_COUNT) return fail(RMB_ERR_ARG, "kind must be 0..5");
+  if (kind < 0 || kind >= rmb::kPublicKinds) return fail(RMB_ERR_ARG, "kind must be 0..5");
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   if (kind == rmb::KIND_TT_TR && !have_vec2) return fail(RMB_ERR_ARG, "RMB_TT_TR needs vec2 (torque)");
   p->eta = eta; p->in_plane = in_plane ? 1 : 0; p->kind = kind;

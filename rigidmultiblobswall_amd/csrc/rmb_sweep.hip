@@ -26,7 +26,11 @@ constexpr sweep_launch_fn sweep_launch() {
 const sweep_launch_fn g_sweeps[rmb::KIND_COUNT][2][2] = {
 #define RMB_ROW(K) {{sweep_launch<K, false, false>(), sweep_launch<K, false, true>()}, {sweep_launch<K, true, false>(), sweep_launch<K, true, true>()}}
     RMB_ROW(rmb::KIND_TT), RMB_ROW(rmb::KIND_TR), RMB_ROW(rmb::KIND_RT), RMB_ROW(rmb::KIND_RR), RMB_ROW(rmb::KIND_TT_TR),
-    RMB_ROW(rmb::KIND_TT_FREE)
+    RMB_ROW(rmb::KIND_TT_FREE),
+    // rotational free-surface kinds: raw heights, the wall = 0 instance serves both columns
+#define RMB_ROW_RAW(K) {{sweep_launch<K, false, false>(), sweep_launch<K, false, true>()}, {sweep_launch<K, false, false>(), sweep_launch<K, false, true>()}}
+    RMB_ROW_RAW(rmb::KIND_TR_FREE), RMB_ROW_RAW(rmb::KIND_RT_FREE), RMB_ROW_RAW(rmb::KIND_RR_FREE), RMB_ROW_RAW(rmb::KIND_TT_TR_FREE)
+#undef RMB_ROW_RAW
 #undef RMB_ROW
 };
 

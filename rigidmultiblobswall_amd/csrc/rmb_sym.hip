@@ -187,6 +187,11 @@ SymXEntry g_symx[SX_COUNT][2][2] = {
     {{make_symx_entry<rmb::OpFreeSurface, false, false>(), make_symx_entry<rmb::OpFreeSurface, false, true>()},
      {make_symx_entry<rmb::OpFreeSurface, false, false>(), make_symx_entry<rmb::OpFreeSurface, false, true>()}},
     RMB_SX_ROW(rmb::OpRadiiTT),
+    // rotational free-surface operations: raw heights as well, per-wave kernel only (symx_coop / symx_two_* / symx32 have none)
+#define RMB_SX_RAW(OP) {{make_symx_entry<OP, false, false>(), make_symx_entry<OP, false, true>()}, {make_symx_entry<OP, false, false>(), make_symx_entry<OP, false, true>()}}
+    RMB_SX_RAW(rmb::OpFreeTR), RMB_SX_RAW(rmb::OpFreeRT), RMB_SX_RAW(rmb::OpFreeRR), RMB_SX_RAW(rmb::OpFreeFusedRow),
+    RMB_SX_RAW(rmb::OpFreeGrand), RMB_SX_RAW(rmb::OpFreeColumnF),
+#undef RMB_SX_RAW
 #define RMB_SX_K(K) RMB_SX_ROW(RMB_SX_KIND(rmb::KIND_TT, K)), RMB_SX_ROW(RMB_SX_KIND(rmb::KIND_TR, K)), \
                     RMB_SX_ROW(RMB_SX_KIND(rmb::KIND_RT, K)), RMB_SX_ROW(RMB_SX_KIND(rmb::KIND_RR, K))
 #define RMB_SX_KIND(KIND, K) rmb::OpKindK<KIND, K>

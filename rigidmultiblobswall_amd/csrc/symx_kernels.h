@@ -219,6 +219,32 @@ struct OpFreeSurface {
   }
 };
 
+// Rotational products above the free surface (context option "free_surface_rotation"; beyond the reference): the blocks
+// TT / TR / RT / RR of the mirror-image system (free_surface_pair, pair_blocks.h: a force mirrors as S f, a torque as
+// -S tau; RPY(d) and RPY(R) evaluated once each and shared by the blocks of the operation).  Forces come first in the
+// record and velocities first in the output, as in OpFusedRow / OpGrand / OpColumnF.  Raw heights: wall = 0 instances only.
+template <bool TT, bool TR, bool RT, bool RR>
+struct OpFreeRot {
+  static constexpr int NIN = ((TT || RT) ? 1 : 0) + ((TR || RR) ? 1 : 0), NOUT = ((TT || TR) ? 1 : 0) + ((RT || RR) ? 1 : 0);
+  static constexpr int TAU = (TT || RT) ? 3 : 0;      // offset of the torque in vi / vj
+  static constexpr int ROT = (TT || TR) ? 3 : 0;      // offset of the angular velocity in ui / t
+  template <bool WALL, bool ACC = false>
+  static __device__ __forceinline__ void pair(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
+                                              const double* vi, const double* vj, double* ui, double* t) {
+    free_surface_pair<TT, TR, RT, RR, ACC>(k, dx, dy, dz, zi, zj, vi, vj, vi + TAU, vj + TAU, ui, ui + ROT, t, t + ROT);
+  }
+  template <bool WALL>
+  static __device__ __forceinline__ void self(const PairConsts& k, double zi, const double* vi, double* ui) {
+    free_surface_self<TT, TR, RT, RR>(k, zi, vi, vi + TAU, ui, ui + ROT);
+  }
+};
+typedef OpFreeRot<false, true, false, false> OpFreeTR;
+typedef OpFreeRot<false, false, true, false> OpFreeRT;
+typedef OpFreeRot<false, false, false, true> OpFreeRR;
+typedef OpFreeRot<true, true, false, false> OpFreeFusedRow;     // u = M_tt f + M_tr tau
+typedef OpFreeRot<true, true, true, true> OpFreeGrand;          // [u; w] = [[M_tt, M_tr], [M_rt, M_rr]] [f; tau]
+typedef OpFreeRot<true, false, true, false> OpFreeColumnF;      // [u; w] = [M_tt; M_rt] f
+
 // Translation mobility of blobs with DIFFERENT radii, sources == targets (the reference's `radii_*` modes call the
 // source->target kernel with the same array on both sides, mobility/mobility.py:1369-1374; pair formulas
 // mobility_numba.py:1480-1658, restated one-sided in st_kernels.h).  The unbounded part (Zuk et al., three regimes)

@@ -50,9 +50,24 @@ def validate(read, uses_dense_blocks=True):
 
   Above a free surface the dense blocks (uses_dense_blocks: the rigid schemes) may be `<backend>_no_wall` -- what a
   reference deck can run: its `C++_free_surface` names a function mobility.py does not define -- or
-  `<backend>_free_surface`, this engine's own blocks (free_surface_blocks below).  The roller schemes do not run there:
-  the reference has no rotational products above a free surface."""
+  `<backend>_free_surface`, this engine's own blocks (free_surface_blocks below).  The roller schemes do not run a
+  reference deck there: the reference has no rotational products above a free surface.
+
+  `domain free_surface` is this engine's own spelling, for roller decks (uses_dense_blocks = False) only: the rotational
+  blocks of the mirror-image system (context option "free_surface_rotation", beyond the reference).  It requires a
+  `<backend>_free_surface` product and returns 'free_surface'; rigid decks keep the reference's spelling."""
   domain = read.domain
+  if domain == "free_surface":
+    if uses_dense_blocks:
+      raise ValueError("domain free_surface: a rigid deck above a free surface keeps the reference's spelling, `domain "
+                       "single_wall` with mobility_vector_prod_implementation <backend>_free_surface; `domain free_surface` "
+                       "is for roller decks")
+    impl = read.mobility_vector_prod_implementation
+    if "radii" in impl or _split(impl)[0] is None or _split(impl)[1] != "free_surface":
+      raise ValueError("mobility_vector_prod_implementation %r: `domain free_surface` needs a <backend>_free_surface "
+                       "product" % (impl,))
+    _check_forces(read)
+    return "free_surface"
   if domain not in ("single_wall", "no_wall", "in_plane"):
     raise ValueError("domain %r: expected single_wall, no_wall or in_plane" % (domain,))
   # (a roller deck, uses_dense_blocks = False, raises here for a free-surface product)
@@ -85,6 +100,12 @@ def validate(read, uses_dense_blocks=True):
       raise ValueError("%s %r is a %s implementation but the deck says `domain %s`: the reference would mix an unbounded "
                        "mobility with wall checks (or the reverse); state the intended one"
                        % (option, getattr(read, option), mode, domain))
+  _check_forces(read)
+  return domain
+
+
+def _check_forces(read):
+  """The force options of a deck the time steppers can honour, or a ValueError."""
   ff = read.blob_blob_force_implementation
   if "radii" in ff:
     raise ValueError("blob_blob_force_implementation %r needs per-blob radii; the time steppers assume one blob radius "
@@ -95,7 +116,6 @@ def validate(read, uses_dense_blocks=True):
   if bb != "None":
     raise ValueError("body_body_force_torque_implementation %r: body-body forces (multi_bodies_functions.py:359-395, a Yukawa "
                      "potential between body centres) are not built; only `None`" % (bb,))
-  return domain
 
 
 def free_surface_blocks(read):

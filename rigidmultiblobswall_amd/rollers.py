@@ -54,8 +54,13 @@ class RollersIntegrator(object):
     self.scheme = scheme
     self.a, self.eta = float(a), float(eta)
     self.domain = domain
-    if domain not in ("single_wall", "no_wall", "in_plane"):
-      raise ValueError("domain must be single_wall, no_wall or in_plane")
+    if domain not in ("single_wall", "no_wall", "in_plane", "free_surface"):
+      raise ValueError("domain must be single_wall, no_wall, in_plane or free_surface")
+    # a stress-free surface at z = 0: the rotational blocks of the mirror-image system (a force mirrors as S f, a torque as
+    # -S tau; beyond the reference, which has M_tt alone there) are an option of the single-GPU context
+    if domain == "free_surface" and ctx is not None and not getattr(ctx, "supports_free_surface_rotation", False):
+      raise ValueError("domain free_surface: this context (%s) does not serve the rotational products above a free surface "
+                       "(a single-GPU MobilityContext does)" % type(ctx).__name__)
     # state and counters, names as quaternion_integrator_rollers.py:36-58
     self.velocities_previous_step = None
     self.deterministic_torque_previous_step = None
@@ -67,7 +72,7 @@ class RollersIntegrator(object):
     self.wall_overlaps = 0
     self.omega_one_roller = np.zeros(3)
     self.free_kinematics = "True"
-    self.hydro_interactions = 1
+    self._hydro_interactions = 1
     self.det_iterations_count = 0
     self.stoch_iterations_count = 0
     self.periodic_length = np.zeros(3)
@@ -96,9 +101,24 @@ class RollersIntegrator(object):
       self._gen, self.seed = seeded_generator(self.device, seed, ctx)   # seed=None: fresh OS entropy, as the reference
     self.ctx = ctx if ctx is not None else MobilityContext(self.device.index or 0)
     self._own_ctx = ctx is None
+    if domain == "free_surface":
+      self.ctx.set_option("free_surface_rotation", 1)
     self.mobility_products = 0
     self._precision = 'double'
     self._force_precision = 'follow'
+
+  @property
+  def hydro_interactions(self):
+    """1 (default): the pair mobility; anything else: independent rollers with the wall's closed-form self mobility
+    (the reference's hydro_interactions switch) -- wall formulas, so refused above a free surface."""
+    return self._hydro_interactions
+
+  @hydro_interactions.setter
+  def hydro_interactions(self, value):
+    if value != 1 and self.domain == "free_surface":
+      raise ValueError("hydro_interactions %r above a free surface: the uncorrelated schemes' closed-form coefficients are "
+                       "wall formulas; only hydro_interactions 1" % (value,))
+    self._hydro_interactions = value
 
   @property
   def precision(self):
@@ -116,6 +136,8 @@ class RollersIntegrator(object):
   def precision(self, value):
     if value not in ('single', 'double'):
       raise ValueError("precision must be 'single' or 'double'")
+    if value == 'single' and self.domain == "free_surface":
+      raise ValueError("precision = 'single' above a free surface: the rotational free surface products are double precision only")
     if value == 'single' and self.kT > 0.0 and self.scheme.startswith("stochastic"):
       # only the stochastic schemes form random finite differences; a deterministic scheme (or kT = 0) with the
       # reference's double-precision rf_delta = 1e-6 may select single precision (the per-step check covers later changes)
@@ -150,7 +172,7 @@ class RollersIntegrator(object):
   def _bind(self, r, wall=None):
     """Make r the configuration the context's products refer to (clamp + B happen on the device)."""
     if wall is None:
-      wall = self.domain != "no_wall"
+      wall = "free_surface" if self.domain == "free_surface" else self.domain != "no_wall"
     self.ctx.set_positions(r.contiguous().view(-1), self.a, self.periodic_length, wall)
 
   def _product(self, kind, vec, vec2=None):
@@ -408,14 +430,14 @@ class RollersIntegrator(object):
   # ---- step bookkeeping -----------------------------------------------------------------------------
   def _valid(self, r):
     """A configuration is rejected when any roller is below the wall plane (:137-142)."""
-    if self.domain != "single_wall":
+    if self.domain not in ("single_wall", "free_surface"):
       return True
     return not bool(torch.any(r[:, 2] < 0.0))
 
   def _accept(self, r_new):
     self.location = r_new
     self.consecutive_rejections = 0
-    if self.domain == "single_wall":
+    if self.domain in ("single_wall", "free_surface"):
       self.wall_overlaps += int(torch.count_nonzero(r_new[:, 2] < self.a))
 
   def _rejected(self):
@@ -606,7 +628,7 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   random numbers are numpy's stream for that seed (the reference calls np.random.seed, :1157-1158)."""
   from . import deck_modes
   from . import structures as st
-  deck_modes.validate(read, uses_dense_blocks=False)    # ValueError for modes this engine does not run
+  domain = deck_modes.validate(read, uses_dense_blocks=False)    # ValueError for modes this engine does not run
   deck_modes.phoretic(read)                             # ValueError for .Laplace files
   locations = []
   body_types = []
@@ -625,7 +647,7 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   from .rigid_integrator import replicate_rng
   rng = replicate_rng(rng, read, ctx, device)
   integ = RollersIntegrator(np.concatenate(locations), read.scheme, read.blob_radius, read.eta,
-                            tolerance=read.solver_tolerance, domain=read.domain, device=device, ctx=ctx, rng=rng)
+                            tolerance=read.solver_tolerance, domain=domain, device=device, ctx=ctx, rng=rng)
   integ.kT = read.kT
   integ.rf_delta = read.rf_delta
   integ.g = read.g
