@@ -183,7 +183,7 @@ int rmb_ctx_release_stream(rmb_ctx* ctx);
  *   "krylov_low_sync" [1]  steps of the native GMRES / Lanczos entries: the launch that subtracts the second Gram-Schmidt projection
  *                          also normalises, with |w2|^2 = |w1|^2 - |h2|^2 from partials of the first update launch (orthonormal
  *                          basis; h2 is rounding-sized): one launch less per iteration; 0 = separate norm / normalisation launch
- *   "lanczos_fuse_finish" [1]  rmb_rigid_lanczos_step_device / rmb_rigid_lanczos_device: the sweep leaves its raw sums and ONE
+ *   "lanczos_fuse_finish" [1]  rmb_rigid_lanczos_device: the sweep leaves its raw sums and ONE
  *                          launch (workgroup = body) finishes them and multiplies by L_b^-1; 0 = finalize and block product as
  *                          two launches (same arithmetic)
  *   "sym_wps"         [0]  symmetric kernels: cap on resident workgroups per CU (0 = occupancy limit)
@@ -324,15 +324,6 @@ int rmb_rigid_operator_device(rmb_ctx* ctx, long n_bodies, long n_b, const doubl
 int rmb_rigid_arnoldi_step_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* A11_dev, const double* A12_dev,
                                   const double* A21_dev, const double* A22_dev, const double* K_dev, double* V_dev, long ldv, long j,
                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev);
-/* One step of the preconditioned Lanczos recursion for the Brownian forcing (P^T M P)^{1/2} z, P = blockdiag(L_b^-T)
- * (stochastic_forcing/stochastic_forcing.py:112-264 driven by multi_bodies/multi_bodies.py:590-614), enqueued by ONE call:
- *   y = P v_i,  w = M_tt y,  w <- P^T w   (two block launches around the pair sweep),
- *   two classical Gram-Schmidt passes of w against v_0 .. v_i: col_dev[i] = h_ii, col_dev[i + 1] = h_{i+1,i} (also to
- *   col_mapped_dev when not NULL), v_{i+1} = w / |w|.
- * Linv_dev: (n_bodies, 3 n_b, 3 n_b) = L_b^-1 as rmb_rigid_preconditioner_device writes it; V_dev rows of ldv >= 3 N doubles;
- * y_dev, w_dev: 3 N doubles of scratch. */
-int rmb_rigid_lanczos_step_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* Linv_dev, double* V_dev, long ldv, long i,
-                                  double eta, double* y_dev, double* w_dev, double* col_dev, double* col_mapped_dev);
 /* The whole right-preconditioned GMRES(restart) of [[M, -K], [-K^T, 0]] x = b (quaternion_integrator_multi_bodies.py:1441-1547
  * -> general_application_utils.py:608-627 -> scipy; all bodies free, one body shape) as ONE call: per iteration one
  * rmb_rigid_arnoldi_step_device and an event; the Givens rotations and the convergence test run on the host INSIDE the
@@ -351,10 +342,14 @@ int rmb_rigid_gmres_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* 
                            double* history, long history_cap, double* rhs_norm);
 /* The whole preconditioned Lanczos forcing  noise = factor * blockdiag(L_b) (P^T M P)^{1/2} z,  P = blockdiag(L_b^-T), of the
  * Brownian rigid-body schemes (quaternion_integrator_multi_bodies.py:966-973 -> stochastic_forcing/stochastic_forcing.py:112-264
- * with the preconditioner of multi_bodies.py:590-614; covariance factor^2 M) as ONE call: per iteration one
- * rmb_rigid_lanczos_step_device and an event; the small tridiagonal eigenproblem (QL sweeps inside the library) and the
- * reference's stopping rule (:239-255: relative change of the noise estimate below tol) run on the host one iteration
- * behind the device.  Linv_dev / Lchol_dev: (n_bodies, 3 n_b, 3 n_b) contiguous factors of the body mobilities
+ * with the preconditioner of multi_bodies.py:590-614; covariance factor^2 M) as ONE call.  Per iteration i one step and an
+ * event:
+ *   y = P v_i,  w = M_tt y,  w <- P^T w   (two block launches around the pair sweep),
+ *   two classical Gram-Schmidt passes of w against v_0 .. v_i, which also store h_ii and h_{i+1,i} into mapped host
+ *   memory, v_{i+1} = w / |w|;
+ * the small tridiagonal eigenproblem (QL sweeps inside the library) and the reference's stopping rule (:239-255: relative
+ * change of the noise estimate below tol) run on the host one iteration behind the device.
+ * Linv_dev / Lchol_dev: (n_bodies, 3 n_b, 3 n_b) contiguous factors of the body mobilities
  * (rmb_rigid_preconditioner_device); z_dev: 3 N standard normals; noise_dev: 3 N doubles out; max_rows: basis vectors the
  * workspace may hold (2 .. 254).  *status: 0 = noise_dev written, *iterations as the reference counts them; 1 = exact
  * breakdown / eigen-solve failure, 2 = more than max_rows basis vectors needed -- then nothing is written, the stream is

@@ -10,7 +10,8 @@ Layout (only what the hot path needs):
   potential.py  blobs_potential_hip / compute_total_energy_hip (the many_bodyMCMC energy surface)
   distributed.py  pair / target sharding over torch.distributed (RCCL) + ReplicatedContext for the callers
 callers built on the path, each mirroring the reference module of the same role:
-  rigid.py             RigidSuspension: saddle-point operator, block-diagonal preconditioner, GMRES
+  rigid.py             RigidSuspension: saddle-point operator, block-diagonal preconditioner, choice of the solver path
+  krylov.py            the lockstep driver, right-preconditioned GMRES and its two static workspaces
   rigid_integrator.py  RigidIntegrator: deterministic / Brownian schemes for rigid multiblobs, deck driver
   rollers.py           RollersIntegrator: single-blob roller schemes, deck driver
   stochastic.py        Lanczos M^{1/2} z (+ dense forcings)

@@ -64,8 +64,6 @@ SYMBOLS = {
     "rmb_lanczos_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_long, ctypes.c_long,
                                          ctypes.c_double, _vp, _lp, _lp, ctypes.POINTER(ctypes.c_int)]),
     "rmb_lanczos_noise_coefficients": (ctypes.c_int, [ctypes.c_long, _dp, _dp, ctypes.c_double, _dp]),
-    "rmb_rigid_lanczos_step_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_double,
-                                                    _vp, _vp, _vp, _vp]),
     "rmb_rigid_arnoldi_step_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long,
                                                     ctypes.c_long, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "rmb_matvec_op_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,

@@ -89,7 +89,7 @@ class MobilityContext(object):
     """Everything that decides WHICH launches a product of this context turns into, as far as this wrapper knows: the
     number of blobs, radius, box and wall of the bound configuration and every option set through set_option().  A
     captured hipGraph of device-path calls stays valid while this is unchanged (positions may move: the packed
-    coordinates are rewritten in place) -- rigid.py keys its captured Arnoldi iterations on it."""
+    coordinates are rewritten in place) -- RigidSuspension keys its captured Arnoldi iterations (krylov._ArnoldiGraphs) on it."""
     return (self._geometry, tuple(self.target_range), tuple(sorted(self._options_set.items())))
 
   def buffers_signature(self):
@@ -347,7 +347,7 @@ class MobilityContext(object):
   def rigid_gmres_device(self, A11, A12, A21, A22, K, b, tol, restart, maxiter, eta):
     """The whole right-preconditioned GMRES of the rigid-body problem in one library call (rmb_rigid_gmres_device); b is
     the RAW right-hand side (scaled to unit norm inside, the solution scaled back).  Returns (x tensor, info dict as
-    rigid.gmres_right_preconditioned, plus rhs_norm)."""
+    krylov.gmres_right_preconditioned, plus rhs_norm)."""
     import torch
     nb, n_b = K.shape[0], K.shape[1] // 3
     for t in (A11, A12, A21, A22, K, b):

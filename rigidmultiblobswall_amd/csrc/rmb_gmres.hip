@@ -5,11 +5,11 @@
 // (quaternion_integrator/quaternion_integrator_multi_bodies.py:1441-1547 -> general_application_utils.py:608-627, restart
 // 60, right preconditioning with the per-body block inverse of multi_bodies.py:548-560).  On the decks it is mostly run on
 // -- tens to hundreds of bodies -- an iteration is seven launches of a few microseconds, so what an iteration costs is
-// the HOST: with the loop in Python (rigid.py: _gmres_steps, one rmb_rigid_arnoldi_step_device call per iteration) 49 us
+// the HOST: with the loop in Python (krylov.py: _gmres_steps, one rmb_rigid_arnoldi_step_device call per iteration) 49 us
 // per iteration against 32-36 us of GPU time (profiles/r5_gmres_step.txt).  Here the loop itself is native: per iteration
 // one rmb_rigid_arnoldi_step_device, one event record, and -- ONE ITERATION LATE, while the device runs the next step --
 // the Givens rotations and the convergence test on the column the Gram-Schmidt kernel stored into mapped host memory.
-// Same algorithm, same stopping rule, same lag policy as rigid.py's loop (which stays for everything this entry does not
+// Same algorithm, same stopping rule, same lag policy as krylov.py's loop (which stays for everything this entry does not
 // cover: several body shapes, prescribed bodies, an initial guess, multi-rank facades):
 //   * two passes of classical Gram-Schmidt per step (rmb_krylov_orthogonalize2_device);
 //   * stop when |g_{j+1}| <= tol |b| (scipy's `tol`, atol = 0), or on an exact breakdown, or after maxiter inner iterations;
@@ -532,8 +532,8 @@ int lanczos_loop(rmb_ctx* c, const char* who, long dim, const double* z_dev, dou
 extern "C" {
 
 // The preconditioned forcing of the rigid-body schemes:  noise = factor * blockdiag(L_b) (P^T M P)^{1/2} z,  P = blockdiag(L_b^-T)
-// (quaternion_integrator_multi_bodies.py:966-973 with the preconditioner of multi_bodies.py:590-614): rigid.py's _lanczos_native
-// loop, natively.
+// (quaternion_integrator_multi_bodies.py:966-973 with the preconditioner of multi_bodies.py:590-614): the loop of
+// stochastic.py behind RigidSuspension.stochastic_forcing, natively.
 int rmb_rigid_lanczos_device(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_dev, const double* Lchol_dev, const double* z_dev,
                              double factor, double tol, long max_iter, long max_rows, double eta, double* noise_dev, long* iterations,
                              long* products, int* status) {

@@ -111,7 +111,7 @@ struct rmb_ctx {
   void* host_in = nullptr;       // ... and the same for its input vectors (two of them: RMB_TT_TR)
   double* host_in_dev = nullptr;
   size_t host_in_cap = 0;
-  long opt_lanczos_fuse_finish = 1; // rmb_rigid_lanczos_step_device: finalize of the sweep + L_b^-1 product in one launch
+  long opt_lanczos_fuse_finish = 1; // rmb_rigid_lanczos_device, every step: finalize of the sweep + L_b^-1 product in one launch
   long opt_krylov_low_sync = 1;     // native GMRES / Lanczos steps: second update + norm (by Pythagoras) + normalisation in one launch
   long opt_gmres_fuse_dots = 1;     // rmb_rigid_gmres_device: the operator's finishing launch also takes the first Gram-Schmidt dots (<= 256 bodies)
   long opt_gmres_fuse_pc = 1;       // rmb_rigid_gmres_device: the normalisation launch also applies the preconditioner for the next step

@@ -369,7 +369,7 @@ static void krylov_layout(long n, long* chunk_out, long* n_chunks_out, size_t* n
   *chunk_out = chunk;
   *n_chunks_out = n_chunks;
   // Sized for the LARGEST basis (kKrMaxRows) whatever `rows` is: the scratch then depends on n only and never moves
-  // while a solve walks up its iteration indices.  rigid.py captures one hipGraph per iteration index with these
+  // while a solve walks up its iteration indices.  krylov.py captures one hipGraph per iteration index with these
   // addresses baked in; a buffer that grew with `rows` was freed and reallocated every 2-3 indices, and the graphs
   // captured for lower indices replayed into freed memory.  ~1 MB for up to 65 536 unknowns, + 512 KB for the
   // per-body partials of the fused first pass.

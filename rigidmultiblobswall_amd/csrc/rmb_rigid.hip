@@ -631,12 +631,12 @@ int plain_tt_with_dots(rmb_ctx* c, const double* v_dev, double eta, double* out_
 int lanczos_step_impl(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_dev, double* V_dev, long ldv, long i, double eta, double* pv_dev,
                       double* mw_dev, double* d_dev, double* col_dev, double* col_mapped_dev, bool pv_ready, bool fuse_next) {
   if (int rc = check_ready(c)) return rc;
-  if (n_bodies < 1 || n_b < 1 || i < 0) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_step_device: bad n_bodies / n_b / i");
-  if (n_bodies * n_b != c->n) return fail(RMB_ERR_STATE, "rmb_rigid_lanczos_step_device: the resident configuration does not hold n_bodies x n_b blobs");
+  if (n_bodies < 1 || n_b < 1 || i < 0) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_device: bad n_bodies / n_b / i");
+  if (n_bodies * n_b != c->n) return fail(RMB_ERR_STATE, "rmb_rigid_lanczos_device: the resident configuration does not hold n_bodies x n_b blobs");
   if (!Linv_dev || !V_dev || !pv_dev || !mw_dev || !d_dev || !col_dev) return fail(RMB_ERR_ARG, "null pointer");
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   const long nn = 3 * n_b, n = c->n, n3 = 3 * n;
-  if (ldv < n3) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_step_device: ldv < 3 N");
+  if (ldv < n3) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_device: ldv < 3 N");
   RMB_HIP(hipSetDevice(c->device));
   const double* v = V_dev + i * ldv;
   // pv = P v with P = blockdiag(L_b^-T): the transposed block is the same memory with the two strides exchanged
@@ -831,12 +831,6 @@ int rmb_rigid_arnoldi_step_device(rmb_ctx* c, long n_bodies, long n_b, const dou
                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev) {
   return arnoldi_step_impl(c, n_bodies, n_b, A11_dev, A12_dev, A21_dev, A22_dev, K_dev, V_dev, ldv, j, eta, z_dev, w_dev, col_dev,
                            col_mapped_dev, false, false);
-}
-
-int rmb_rigid_lanczos_step_device(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_dev, double* V_dev, long ldv, long i,
-                                  double eta, double* y_dev, double* w_dev, double* col_dev, double* col_mapped_dev) {
-  // y = P v_i, w = M y (or the raw sums of the sweep), then y <- P^T M y in y's place and its orthogonalisation
-  return lanczos_step_impl(c, n_bodies, n_b, Linv_dev, V_dev, ldv, i, eta, y_dev, w_dev, y_dev, col_dev, col_mapped_dev, false, false);
 }
 
 }  // extern "C"

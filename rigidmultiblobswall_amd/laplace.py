@@ -203,7 +203,7 @@ class PhoreticSlip(object):
     Laplace problem once."""
     if self._slip is not None and self._key is susp.location:
       return self._slip
-    from .rigid import gmres_right_preconditioned
+    from .krylov import gmres_right_preconditioned
     from .rigid_integrator import lab_frame_slip
     ctx = self._ctx
     r = susp.r_dev.view(-1, 3)

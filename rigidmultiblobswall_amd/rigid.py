@@ -17,16 +17,20 @@ with numpy + scipy on the host, here with every vector resident in HBM:
     to 1 (general_application_utils.py:514-627, quaternion_integrator_multi_bodies.py:1518-1537).
     Krylov vectors stay on the device; per iteration only the new Hessenberg column crosses PCIe.
 
+This module holds the suspension: configuration, operator, preconditioner, and which solver path a call takes
+(RigidSuspension._gmres_path, _lanczos_native).  The iterations themselves -- the GMRES coroutine, its two static workspaces
+and the lockstep driver -- are krylov.py; the Lanczos coroutine is stochastic.py.
+
 PyTorch is used for device memory and batched small dense algebra only.
 """
-import gc
-import math
-import os
+import contextlib
 
 import numpy as np
 import torch
 
 from .context import MobilityContext
+from .krylov import (_ArnoldiGraphs, _ArnoldiNative, _gmres_steps, drive, gmres_pair_right_preconditioned,
+                     gmres_right_preconditioned, switched_off)
 
 
 def quaternion_rotation_matrix(q):
@@ -277,10 +281,6 @@ class RigidSuspension(object):
     if ns is not None:
       ns.close()
       self._arnoldi_native = None
-    lw = getattr(self, "_lanczos_ws", None)
-    if lw is not None:
-      lw["mapped"].close()
-      self._lanczos_ws = None
     if self._own_ctx:
       self.ctx.close()
 
@@ -548,12 +548,8 @@ class RigidSuspension(object):
     x0: optional initial guess in the units of x.  Returns (x tensor, info)."""
     if self.groups[0].Lchol is None:
       self.build_preconditioner()
-    if (x0 is None and self.native_gmres is not False and os.environ.get("RMB_NATIVE_GMRES", "") != "0"
-        and self._native_step_applies(restart)):
-      # The whole loop inside the library (rmb_rigid_gmres_device): the norm of the right-hand side, per iteration one step
-      # call and one event, the Givens rotations and the convergence test in C one iteration behind the device -- the
-      # Python loop below costs 49 us of host time per iteration against 32-36 us of GPU time on a small deck
-      # (profiles/r5_gmres_step.txt).
+    path, ws = self._gmres_path(restart, x0)
+    if path == "library":
       g = self.groups[0]
       sol, info = self.ctx.rigid_gmres_device(g.A11, g.A12, g.A21, g.A22, g.K, rhs.contiguous(), tol, restart, maxiter, self.eta)
       if info["rhs_norm"] == 0.0:
@@ -566,69 +562,86 @@ class RigidSuspension(object):
     if nrm == 0.0:
       return torch.zeros_like(rhs), dict(iterations=0, residual=0.0, converged=True, history=[])
     ortho = self._ortho(restart)
-    ns = self._native_arnoldi(restart)
-    if ns is not None:
-      # One C call per Arnoldi iteration enqueues all of its launches (rmb_rigid_arnoldi_step_device: preconditioner blocks,
-      # pair sweep, finishing launch with the K products, fused Gram-Schmidt that also stores the Hessenberg column into
-      # mapped host memory): 7 launches from one host call, no graph, no copy command.
-      ns.bind(self)
+    sync = lag = None
+    if path == "step":
+      ws.bind(self)
+    elif path == "graphs":
+      ws.bind(self._graph_signature(), self.apply_operator, self.apply_preconditioner, ortho, self._count_operator)
+    else:                      # only the plain loop is told how the context shares scalars and whether to lag
+      sync, lag = getattr(self.ctx, "sync_scalars", None), getattr(self, "gmres_lag", None)
+    with (ws.solve_stream(self.ctx) if path == "graphs" else contextlib.nullcontext()) as caller_stream:
       sol, info = gmres_right_preconditioned(self.apply_operator, self.apply_preconditioner, rhs / nrm, tol=tol,
                                              restart=restart, maxiter=maxiter, x0=None if x0 is None else x0 / nrm,
-                                             ws=ns, on_replay=self._count_operator, ortho=ortho)
-      info["rhs_norm"] = nrm
-      info["native_steps"] = ns.steps_this_solve
-      return sol * nrm, info
-    ws = self._arnoldi_graphs(restart)
-    if ws is None:
-      sol, info = gmres_right_preconditioned(self.apply_operator, self.apply_preconditioner, rhs / nrm, tol=tol,
-                                             restart=restart, maxiter=maxiter, x0=None if x0 is None else x0 / nrm,
-                                             sync=getattr(self.ctx, "sync_scalars", None), lag=getattr(self, "gmres_lag", None),
-                                             ortho=ortho)
-      info["rhs_norm"] = nrm
-      return sol * nrm, info
-    # Small systems: the device side of every Arnoldi iteration (preconditioner, operator, Gram-Schmidt, normalisation,
-    # column to page-locked memory: ~16 launches) is one captured hipGraph per iteration index, replayed from the third
-    # solve on.  The whole solve runs on the workspace's stream (a capture cannot happen on the default stream, and the
-    # context must already enqueue on the capturing stream when a capture begins).
-    cur = torch.cuda.current_stream(self.device)
-    ws.stream.wait_stream(cur)
-    with torch.cuda.stream(ws.stream):
-      self.ctx._follow_torch_stream()
-      ws.begin_solve()
-      sol, info = gmres_right_preconditioned(self.apply_operator, self.apply_preconditioner, rhs / nrm, tol=tol,
-                                             restart=restart, maxiter=maxiter, x0=None if x0 is None else x0 / nrm,
-                                             ws=ws, on_replay=self._count_operator, ortho=ortho)
+                                             sync=sync, lag=lag, ws=ws, ortho=ortho)
       sol = sol * nrm
-    cur.wait_stream(ws.stream)
-    sol.record_stream(cur)
     info["rhs_norm"] = nrm
-    info["graph_replays"] = ws.replays_this_solve
+    if path == "step":
+      info["native_steps"] = ws.steps_this_solve
+    elif path == "graphs":
+      sol.record_stream(caller_stream)
+      info["graph_replays"] = ws.replays_this_solve
     return sol, info
 
   fused_operator = True       # False: the product and the K products as separate launches (A/B, tests)
-  native_step = None          # None = automatic, False = never: one C call per Arnoldi iteration (_ArnoldiNative)
   native_gmres = None         # None = automatic, False = never: the whole GMRES loop in one C call (rmb_rigid_gmres_device)
+  native_step = None          # None = automatic, False = never: one C call per Arnoldi iteration (_ArnoldiNative)
+  # `gmres_graph`: None = automatic (on for a plain single-GPU context up to `gmres_graph_max_blobs` blobs, where the
+  # iteration is launch-bound: profiles/r4_gmres_graph.txt), True / False = forced.  RMB_GMRES_GRAPH=0 turns it off.
+  gmres_graph = None
+  gmres_graph_max_blobs = 4096
 
-  def _native_step_applies(self, restart):
-    want = self.native_step
-    if os.environ.get("RMB_NATIVE_STEP", "") == "0":
-      want = False
-    return not (want is False or self.gmres_graph is True or self.free is not None or len(self.groups) != 1 or self.device.type != "cuda"
-                or type(self.ctx) is not MobilityContext or self._native_products() is not self.ctx or not self.fused_operator
-                or getattr(self, "gmres_lag", None) is False or not (0 < restart < 256))
+  def _gmres_path(self, restart, x0=None, native=True):
+    """Which of the four GMRES paths solve(rhs, restart=restart, x0=x0) takes, and the path's workspace (solve() binds it
+    once the right-hand side is known not to vanish).  native = False: the choice without the library's two paths (what
+    _arnoldi_graphs asks).  The only reader of native_gmres, native_step, gmres_graph and RMB_NATIVE_GMRES / RMB_NATIVE_STEP /
+    RMB_GMRES_GRAPH (each "0" = off, whatever the attribute says).
 
-  def _native_arnoldi(self, restart):
-    """The one-call-per-iteration workspace for solve(), or None.  Applies to what rmb_rigid_arnoldi_step_device covers: one
-    body shape of at most `native_products_max_blobs` blobs, all bodies free, a plain single-GPU context, the host bookkeeping one iteration late.
-    `gmres_graph = True` (forced captured iterations) and `native_step = False` / RMB_NATIVE_STEP=0 turn it off."""
-    if not self._native_step_applies(restart):
-      return None
-    ns = getattr(self, "_arnoldi_native", None)
-    if ns is None or ns.m != restart or ns.n != self.size:
-      if ns is not None:
-        ns.close()
-      ns = self._arnoldi_native = _ArnoldiNative(self.size, restart, self.device)
-    return ns
+      "library", None   The whole loop inside the library (rmb_rigid_gmres_device): the norm of the right-hand side, per
+                        iteration one step call and one event, the Givens rotations and the convergence test in C one
+                        iteration behind the device -- the Python loop costs 49 us of host time per iteration against
+                        32-36 us of GPU time on a small deck (profiles/r5_gmres_step.txt).  Covers what the step call
+                        covers, without an initial guess.
+      "step", ws        One C call per Arnoldi iteration (_ArnoldiNative) under the Python loop.  Covers one body shape of
+                        at most `native_products_max_blobs` blobs, all bodies free, a plain single-GPU context, the host
+                        bookkeeping one iteration late.  `gmres_graph = True` (forced captured iterations) turns it off.
+      "graphs", ws      Small systems: the device side of every Arnoldi iteration (~16 launches) is one captured hipGraph
+                        per iteration index, replayed from the third solve on (_ArnoldiGraphs).
+      "eager", None     The plain loop: every launch enqueued from Python."""
+    plain = (self.device.type == "cuda" and type(self.ctx) is MobilityContext and getattr(self, "gmres_lag", None) is not False)
+    step = (native and plain and self.native_step is not False and not switched_off("RMB_NATIVE_STEP") and self.gmres_graph is not True
+            and self.free is None and len(self.groups) == 1 and self._native_products() is self.ctx and self.fused_operator
+            and 0 < restart < 256)
+    if step and x0 is None and self.native_gmres is not False and not switched_off("RMB_NATIVE_GMRES"):
+      return "library", None
+    if step:
+      ws = getattr(self, "_arnoldi_native", None)
+      if ws is None or ws.m != restart or ws.n != self.size:
+        if ws is not None:
+          ws.close()
+        ws = self._arnoldi_native = _ArnoldiNative(self.size, restart, self.device)
+      return "step", ws
+    graph = False if switched_off("RMB_GMRES_GRAPH") else self.gmres_graph
+    if graph is None:
+      graph = self.n_blobs <= self.gmres_graph_max_blobs
+    if not (graph and plain and self.ctx.get_option("timing") == 0):
+      return "eager", None
+    ws = getattr(self, "_arnoldi_ws", None)
+    if ws is None or ws.m != restart:
+      ws = self._arnoldi_ws = _ArnoldiGraphs(self.size, restart, self.device)
+    ws.buffers = getattr(self.ctx, "buffers_signature", None)
+    if self._ortho(restart) is not None and not switched_off("RMB_MAPPED_COLUMNS"):    # "0" keeps the copy node in the captured iteration
+      ws.use_mapped_columns()
+    return "graphs", ws
+
+  def _graph_signature(self):
+    """Everything the captured iterations hold by address or depend on by value: the graphs go when it changes."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return (self.ctx.launch_signature(), self.eta, self._native_blocks() is not None, ptr(self.free), ptr(self.prescribed_velocity),
+            tuple(tuple(ptr(t) for t in (g.K, g.A11, g.A12, g.A21, g.A22)) for g in self.groups))
+
+  def _arnoldi_graphs(self, restart):
+    """The captured-iteration workspace for solve(), or None when the plain loop is to run."""
+    return self._gmres_path(restart, native=False)[1]
 
   # `native_helpers`: the O(N) pieces between two sweeps (K / K^T products, the preconditioner's four blocks, the
   # Gram-Schmidt of an Arnoldi step) as the library's own kernels (csrc/rmb_krylov.hip) instead of batched-GEMM / GEMV
@@ -641,7 +654,7 @@ class RigidSuspension(object):
     are rank-local O(N) work on replicated vectors with fixed-order reductions, so every rank computes the same bits."""
     want = self.native_helpers
     if want is None:
-      want = os.environ.get("RMB_NATIVE_HELPERS", "") != "0"
+      want = not switched_off("RMB_NATIVE_HELPERS")
     if not want or self.device.type != "cuda":
       return None
     if type(self.ctx) is MobilityContext:
@@ -665,32 +678,6 @@ class RigidSuspension(object):
   def _count_operator(self):
     self.matvec_count += 1
     self.sweep_count += 1
-
-  # `gmres_graph`: None = automatic (on for a plain single-GPU context up to `gmres_graph_max_blobs` blobs, where the
-  # iteration is launch-bound: profiles/r4_gmres_graph.txt), True / False = forced.  RMB_GMRES_GRAPH=0 turns it off.
-  gmres_graph = None
-  gmres_graph_max_blobs = 4096
-
-  def _arnoldi_graphs(self, restart):
-    """The captured-iteration workspace for solve(), or None when the plain loop is to run."""
-    want = self.gmres_graph
-    if os.environ.get("RMB_GMRES_GRAPH", "") == "0":
-      want = False
-    if want is None:
-      want = self.n_blobs <= self.gmres_graph_max_blobs
-    if (not want or self.device.type != "cuda" or type(self.ctx) is not MobilityContext
-        or getattr(self, "gmres_lag", None) is False or self.ctx.get_option("timing") != 0):
-      return None
-    ws = getattr(self, "_arnoldi_ws", None)
-    if ws is None or ws.m != restart:
-      ws = self._arnoldi_ws = _ArnoldiGraphs(self.size, restart, self.device)
-    ws.buffers = getattr(self.ctx, "buffers_signature", None)
-    if self._ortho(restart) is not None and os.environ.get("RMB_MAPPED_COLUMNS", "") != "0":
-      ws.use_mapped_columns()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    ws.bind((self.ctx.launch_signature(), self.eta, self._native_blocks() is not None, ptr(self.free), ptr(self.prescribed_velocity),
-             tuple(tuple(ptr(t) for t in (g.K, g.A11, g.A12, g.A21, g.A22)) for g in self.groups)))
-    return ws
 
   def solve_mixed_precision(self, rhs, tol=1e-8, inner_tol=3e-5, restart=60, maxiter=1000, max_outer=8):
     """The same saddle-point solve by iterative refinement with a single-precision inner operator -- MI355X issues
@@ -821,25 +808,10 @@ class RigidSuspension(object):
 
   def run_lockstep(self, tasks):
     """Advance independent tasks that all need products with the mobility of the BOUND configuration (GMRES solves,
-    Lanczos recursions, single products): every round collects one request per running task and serves them with one
-    k-vector pass over the pairs (mobility_times_lambdas).  Each task sees exactly the iterates it would see alone.
+    Lanczos recursions, single products) with krylov.drive: every round's requests, one per running task, are served with
+    one k-vector pass over the pairs (mobility_times_lambdas).  Each task sees exactly the iterates it would see alone.
     Returns the tasks' return values, in order."""
-    n = len(tasks)
-    requests, results, running = [None] * n, [None] * n, [True] * n
-    for k, t in enumerate(tasks):
-      try:
-        requests[k] = next(t)
-      except StopIteration as done:
-        results[k], running[k] = done.value, False
-    while any(running):
-      act = [k for k in range(n) if running[k]]
-      answers = self.mobility_times_lambdas([requests[k] for k in act])
-      for k, ans in zip(act, answers):
-        try:
-          requests[k] = tasks[k].send(ans)
-        except StopIteration as done:
-          results[k], running[k] = done.value, False
-    return results
+    return drive(tasks, self.mobility_times_lambdas)
 
   def solve_mobility_problem(self, slip=None, force_torque=None, tol=1e-8, restart=60, maxiter=1000, x0=None,
                              mixed_precision=False):
@@ -916,127 +888,37 @@ class RigidSuspension(object):
                                       L_mult=lambda x: self._blockdiag(x, "Lchol"), z=z, print_residual=print_residual,
                                       device=self.device, sync=getattr(self.ctx, "sync_scalars", None), ortho=self._ortho(0))
 
-  native_lanczos = None       # None = automatic, False = never: the library's Lanczos step / loop (_lanczos_native)
-  native_lanczos_loop = None  # None = automatic, False = one C call per iteration under a Python loop instead of rmb_rigid_lanczos_device
+  native_lanczos = None       # None = automatic, False = never: the library's Lanczos loop (_lanczos_native)
   lanczos_native_loop_calls = 0
   lanczos_native_rows = 96    # basis rows of the native loop; a forcing that needs more falls back to the generic loop
   lanczos_native_max_blobs = 20000  # above, the iteration it discards at the end (a whole pair sweep) costs more than the host waits it
                                     # saves: 12 288 blobs 5.33 -> 4.55 ms per forcing, 16 392: 8.23 -> 7.63, 24 576: level (exp_lanczos_threshold.py)
 
   def _lanczos_native(self, z, factor, tol, print_residual, max_iter=1000):
-    """The preconditioned Lanczos forcing inside the library: the whole loop in one call (rmb_rigid_lanczos_device, the
-    default), or -- `native_lanczos_loop = False`, RMB_NATIVE_LANCZOS_LOOP=0, print_residual -- the loop below with
-    ONE library call per iteration (rmb_rigid_lanczos_step_device: two block
-    launches around the pair sweep + the fused Gram-Schmidt, which also stores h_ii and h_{i+1,i} into mapped host
-    memory), the host side (the small tridiagonal eigenproblem and the reference's stopping rule,
-    stochastic_forcing.py:239-255) running ONE ITERATION LATE -- so the device never waits for numpy.  Same iterates,
+    """The preconditioned Lanczos forcing inside the library, the whole loop in one call (rmb_rigid_lanczos_device: per
+    iteration two block launches around the pair sweep + the fused Gram-Schmidt, which also stores h_ii and h_{i+1,i}
+    into mapped host memory; the small tridiagonal eigenproblem and the reference's stopping rule,
+    stochastic_forcing.py:239-255, in C ONE ITERATION LATE -- so the device never waits for the host).  Same iterates,
     coefficients and iteration count as stochastic.stochastic_forcing_lanczos; the price is one discarded iteration at
-    the end.  Returns (noise, iterations), or None when it does not apply (several body shapes, more than 32 blobs per
-    body, a facade context, an exact breakdown, more iterations than `lanczos_native_rows`) -- the caller then runs the
-    generic loop from the start."""
-    from .stochastic import _noise_coefficients
-    want = self.native_lanczos
-    if os.environ.get("RMB_NATIVE_LANCZOS", "") == "0":
-      want = False
-    if (want is False or factor == 0.0 or len(self.groups) != 1 or self.device.type != "cuda" or type(self.ctx) is not MobilityContext
-        or self._native_products() is not self.ctx or (want is None and self.n_blobs > self.lanczos_native_max_blobs)):
-      return None
+    the end.  Returns (noise, iterations), or None when it does not apply (several body shapes, more than
+    `native_products_max_blobs` blobs per body, a facade context, print_residual: the lines are the generic loop's) or
+    the library hands the forcing back (an exact breakdown, more iterations than `lanczos_native_rows`) -- the caller
+    then runs the generic loop from the start."""
+    want = False if switched_off("RMB_NATIVE_LANCZOS") else self.native_lanczos
     g = self.groups[0]
-    n3, cap = 3 * self.n_blobs, int(self.lanczos_native_rows)
+    cap = int(self.lanczos_native_rows)
+    if (want is False or factor == 0.0 or len(self.groups) != 1 or self.device.type != "cuda" or type(self.ctx) is not MobilityContext
+        or self._native_products() is not self.ctx or (want is None and self.n_blobs > self.lanczos_native_max_blobs)
+        or print_residual or not 2 <= cap <= 254 or not g.Lchol.is_contiguous()):
+      return None
     if not g.Linv.is_contiguous():
       g.Linv = g.Linv.contiguous()
-    loop = self.native_lanczos_loop
-    if os.environ.get("RMB_NATIVE_LANCZOS_LOOP", "") == "0":
-      loop = False
-    if loop is not False and not print_residual and 2 <= cap <= 254 and g.Lchol.is_contiguous():
-      # the loop itself inside the library (rmb_rigid_lanczos_device): no Python between the iterations
-      zt = torch.as_tensor(z, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
-      noise, its, products = self.ctx.rigid_lanczos_device(g.Linv, g.Lchol, zt, factor, tol, max_iter, cap, self.eta)
-      self.matvec_count += products
-      self.sweep_count += products
-      self.lanczos_native_loop_calls += 1
-      return None if noise is None else (noise, its)
-    ws = getattr(self, "_lanczos_ws", None)
-    if ws is None or ws["n3"] != n3 or ws["cap"] != cap:
-      from .context import MappedHostArray
-      ws = self._lanczos_ws = dict(n3=n3, cap=cap, V=torch.empty((cap + 1, n3), dtype=torch.float64, device=self.device),
-                                   col=torch.zeros((cap, cap + 2), dtype=torch.float64, device=self.device),
-                                   y=torch.empty(n3, dtype=torch.float64, device=self.device),
-                                   w=torch.empty(n3, dtype=torch.float64, device=self.device), mapped=MappedHostArray((cap, cap + 2)),
-                                   events=[torch.cuda.Event(), torch.cuda.Event()])
-    V, host = ws["V"], ws["mapped"].array
-    z = torch.as_tensor(z, dtype=torch.float64, device=self.device).reshape(-1)
-    v_norm = float(torch.linalg.norm(z))
-    V[0] = z / v_norm
-    ctx = self.ctx
-    ctx._follow_torch_stream()
-    stream = torch.cuda.current_stream(self.device)
-    fn = ctx._lib.rmb_rigid_lanczos_step_device
-    if not g.Linv.is_contiguous():
-      g.Linv = g.Linv.contiguous()
-    head = (ctx._h, g.K.shape[0], g.n_b, g.Linv.data_ptr(), V.data_ptr(), V.stride(0))
-    tail = (float(self.eta), ws["y"].data_ptr(), ws["w"].data_ptr())
-    col_ptr, mapped_ptr, row = ws["col"].data_ptr(), ws["mapped"].dev_ptr, 8 * (cap + 2)
-    if not g.Linv.is_contiguous():
-      g.Linv = g.Linv.contiguous()
-    h_diag, h_sup = [], []
-    coef_old, coef, its, done = None, None, None, False
-
-    def enqueue(i):
-      rc = fn(*head, i, *tail, col_ptr + i * row, mapped_ptr + i * row)
-      if rc != 0:
-        from . import _lib
-        _lib.check(rc)
-      self.matvec_count += 1
-      self.sweep_count += 1
-      ws["events"][i & 1].record(stream)
-
-    def finish(i):
-      """Host side of iteration i (its two coefficients are in mapped memory once its event has completed).  True = stop."""
-      nonlocal coef_old, coef, its
-      ws["events"][i & 1].synchronize()
-      hd_f, hs_f = float(host[i, i]), float(host[i, i + 1])
-      if not (hs_f > 0 and np.isfinite(hs_f)):
-        return None                          # exact breakdown: rare; the generic loop handles it
-      h_diag.append(hd_f)
-      h_sup.append(hs_f)
-      coef = _noise_coefficients(h_diag, h_sup, i + 1, v_norm * factor)
-      if i > 0:
-        old = np.concatenate([coef_old, [0.0]])
-        old_norm = np.linalg.norm(old)
-        diff = np.linalg.norm(coef - old)
-        if print_residual:
-          if i == 1:
-            print('lanczos =  0 1')
-          print('lanczos = ', i, diff / old_norm)
-        if diff / max(old_norm, np.finfo(float).eps) < tol:
-          its = i
-          return True
-      coef_old = coef
-      return False
-
-    enqueue(0)
-    i = 0
-    while True:
-      nxt = i + 1
-      if nxt < cap and nxt <= max_iter:
-        enqueue(nxt)                         # the device goes on while the host looks at iteration i
-      stop = finish(i)
-      if stop is None:
-        torch.cuda.synchronize(self.device)
-        return None
-      if stop:
-        break
-      if nxt >= cap or nxt > max_iter:
-        if nxt > max_iter:
-          its = max_iter
-          break
-        torch.cuda.synchronize(self.device)  # more basis rows needed than the workspace holds: generic loop
-        return None
-      i = nxt
-    k = len(coef)
-    noise = V[:k].t() @ torch.as_tensor(coef, dtype=torch.float64, device=self.device)
-    return self._blockdiag(noise, "Lchol").reshape(-1), its
+    zt = torch.as_tensor(z, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
+    noise, its, products = self.ctx.rigid_lanczos_device(g.Linv, g.Lchol, zt, factor, tol, max_iter, cap, self.eta)
+    self.matvec_count += products
+    self.sweep_count += products
+    self.lanczos_native_loop_calls += 1
+    return None if noise is None else (noise, its)
 
   def stochastic_forcing_pair(self, z_a, factor_a, z_b, factor_b, tol=1e-8, print_residual=False):
     """Two forcings with the same mobility in lockstep (stochastic_forcing_lanczos_pair): one two-vector pair sweep per
@@ -1049,387 +931,3 @@ class RigidSuspension(object):
     return stochastic_forcing_lanczos_pair((factor_a, factor_b), (z_a, z_b), one, two, tolerance=tol,
                                            L_mult=lambda x: self._blockdiag(x, "Lchol"), print_residual=print_residual,
                                            device=self.device, sync=getattr(self.ctx, "sync_scalars", None), ortho=self._ortho(0))
-
-# page-locked staging rows for the Hessenberg columns of running solves (allocated once, handed out per solve)
-_pinned_pool = []
-
-
-class _ArnoldiNative(object):
-  """Static workspace of GMRES(restart) whose device side of an iteration is ONE call into the library
-  (MobilityContext.rigid_arnoldi_step_device).  Same interface as _ArnoldiGraphs towards _gmres_steps: V, cols, host_cols
-  (here page-locked memory mapped into the device's address space: the Gram-Schmidt kernel stores the column there
-  itself) and run(j, ...)."""
-
-  def __init__(self, n, restart, device):
-    from .context import MappedHostArray
-    self.n, self.m, self.device = int(n), int(restart), device
-    self.V = torch.zeros((self.m + 1, self.n), dtype=torch.float64, device=device)
-    self.cols = torch.zeros((self.m, self.m + 2), dtype=torch.float64, device=device)
-    self.z = torch.empty(self.n, dtype=torch.float64, device=device)
-    self.w = torch.empty(self.n, dtype=torch.float64, device=device)
-    self.mapped = MappedHostArray((self.m, self.m + 2))
-    self.host_cols = self.mapped.array
-    self.owner = None
-    self.steps = self.steps_this_solve = 0
-
-  def bind(self, owner):
-    """Once per solve: everything of the step call that does not change from one iteration to the next, as plain integers
-    (building sixteen ctypes objects per iteration costs more host time than the GPU needs for the iteration)."""
-    self.owner = owner
-    self.steps_this_solve = 0
-    ctx, g = owner.ctx, owner.groups[0]
-    for t in (g.A11, g.A12, g.A21, g.A22, g.K):
-      assert t.is_contiguous()
-    ctx._follow_torch_stream()                   # the solve stays on the stream that is current now
-    self._fn = ctx._lib.rmb_rigid_arnoldi_step_device
-    self._head = (ctx._h, g.K.shape[0], g.K.shape[1] // 3, g.A11.data_ptr(), g.A12.data_ptr(), g.A21.data_ptr(), g.A22.data_ptr(),
-                  g.K.data_ptr(), self.V.data_ptr(), self.V.stride(0))
-    self._tail = (float(owner.eta), self.z.data_ptr(), self.w.data_ptr())
-    self._cols_ptr, self._mapped_ptr, self._row = self.cols.data_ptr(), self.mapped.dev_ptr, 8 * (self.m + 2)
-
-  def run(self, j, body, on_replay=None):
-    rc = self._fn(*self._head, j, *self._tail, self._cols_ptr + j * self._row, self._mapped_ptr + j * self._row)
-    if rc != 0:
-      from . import _lib
-      _lib.check(rc)
-    if on_replay is not None:
-      on_replay()
-    self.steps += 1
-    self.steps_this_solve += 1
-
-  def close(self):
-    self.owner = None
-    if self.mapped is not None:
-      self.host_cols = None
-      self.mapped.close()
-      self.mapped = None
-
-
-class _ArnoldiGraphs(object):
-  """Static workspace of GMRES(restart) on one system size and, per iteration index j, a captured hipGraph of everything
-  the DEVICE does in that iteration.  On systems of a few thousand blobs an iteration is ~16 small launches whose
-  enqueueing costs more host time than they take to run (tools/experiments/exp_small_deck_gmres.py: ~200 us per
-  iteration around a 10-20 us blob product); replaying a graph is one call.
-
-  An index j runs eagerly the first time it is met, is captured once `capture_after` solves have been seen, and is
-  replayed from then on.  The graphs hold pointers: to this workspace, to the operator's K and preconditioner blocks
-  (rewritten in place by set_configuration / build_preconditioner), to the context's packed positions and accumulators.
-  bind() drops them whenever the signature the owner hands over changes."""
-  capture_after = 2
-
-  def __init__(self, n, restart, device):
-    self.n, self.m, self.device = int(n), int(restart), device
-    self.V = torch.zeros((self.m + 1, self.n), dtype=torch.float64, device=device)
-    self.cols = torch.zeros((self.m, self.m + 2), dtype=torch.float64, device=device)
-    self.host_cols = torch.zeros((self.m, self.m + 2), dtype=torch.float64).pin_memory()
-    # The fused Gram-Schmidt kernel can store the new Hessenberg column straight into page-locked memory that is mapped
-    # into the device's address space (context.MappedHostArray): one graph node (the copy) less per iteration.  Set up by
-    # the owner when its context has the entry point; host_cols then IS that memory (a numpy array).
-    self.mapped_cols = None
-    self.stream = torch.cuda.Stream(device)
-    self.graphs, self.seen, self.signature = {}, set(), None
-    self.solves = self.captures = self.replays = self.replays_this_solve = 0
-    self.buffers = None               # callable: the context's buffers_signature() (set by the owner), checked before a replay
-    self.buffers_at_capture = None
-    self.stale_drops = 0
-
-  def bind(self, signature):
-    if signature != self.signature:
-      self.release()
-      self.signature = signature
-
-  def use_mapped_columns(self):
-    if self.mapped_cols is None:
-      from .context import MappedHostArray
-      self.mapped_cols = MappedHostArray((self.m, self.m + 2))
-      self.host_cols = self.mapped_cols.array
-
-  def col_mapped_ptr(self, j):
-    """Device address of row j of the mapped column buffer, or 0."""
-    return 0 if self.mapped_cols is None else self.mapped_cols.dev_ptr + 8 * j * (self.m + 2)
-
-  def release(self):
-    """Destroy the graphs now (a safe point: nothing is capturing) rather than whenever the collector finds them.  A graph
-    of the previous solve may still be executing -- the lagged bookkeeping leaves its last, discarded iteration in flight,
-    and a stale-buffer drop happens in the middle of a solve: wait for the device first, destroying an executing
-    hipGraphExec is not something to rely on (an intermittent hang of a slip-scheme test on the box was traced to here)."""
-    if self.graphs and self.device.type == "cuda":
-      torch.cuda.synchronize(self.device)
-    self.graphs.clear()
-    self.seen.clear()
-    self.solves = 0
-
-  def begin_solve(self):
-    self.solves += 1
-    self.replays_this_solve = 0
-
-  def run(self, j, body, on_replay=None):
-    g = self.graphs.get(j)
-    if g is not None and self.buffers is not None and self.buffers() != self.buffers_at_capture:
-      # The graph holds the addresses of the context's internal buffers by value, and one of them has moved since the
-      # capture (another, larger suspension used the shared context; a product grew a scratch buffer): every graph is
-      # stale.  Same treatment as a changed signature in bind(): drop them, run eagerly again, capture afresh after
-      # `capture_after` further solves.
-      self.release()
-      self.solves = 1            # this solve is the first of the new series
-      self.stale_drops += 1
-      g = None
-    if g is None:
-      if j not in self.seen or self.solves <= self.capture_after:
-        body()                                   # eager: also warms every library call of this iteration's shapes
-        self.seen.add(j)
-        return
-      g = torch.cuda.CUDAGraph()
-      torch.cuda.synchronize(self.device)
-      # No cyclic garbage collection while the stream is capturing: collecting a dead CUDAGraph (another suspension's,
-      # say) calls hipGraphDestroy, which HIP refuses during a capture -- and the refusal surfaces in a destructor.
-      gc_was_on = gc.isenabled()
-      gc.disable()
-      try:
-        g.capture_begin(capture_error_mode="thread_local")
-        try:
-          body()                                 # enqueues nothing: recorded into the graph (the owner counts it)
-        finally:
-          g.capture_end()
-      finally:
-        if gc_was_on:
-          gc.enable()
-      if self.buffers is not None:
-        now = self.buffers()
-        if self.graphs and now != self.buffers_at_capture:    # the eager warm-ups have sized everything: never expected
-          self.graphs.clear()
-          self.stale_drops += 1
-        self.buffers_at_capture = now
-      self.graphs[j] = g
-      self.captures += 1
-    elif on_replay is not None:
-      on_replay()
-    g.replay()
-    self.replays += 1
-    self.replays_this_solve += 1
-
-
-def _pinned_columns(rows, cols):
-  for k, t in enumerate(_pinned_pool):
-    if t.shape[0] >= rows and t.shape[1] >= cols:
-      return _pinned_pool.pop(k)
-  return torch.empty((max(rows, 62), max(cols, 63)), dtype=torch.float64).pin_memory()
-
-
-def _gmres_steps(Minv, b, tol, restart, maxiter, x0, sync, lag=None, ws=None, A=None, on_replay=None, ortho=None):
-  """GMRES(restart) on A.Minv written as a coroutine: it YIELDS every vector it needs the operator applied to and
-  receives A(vector) back, so one driver can serve a single solve (gmres_right_preconditioned) or advance two solves
-  in lockstep and hand both requests to a two-vector operator (gmres_pair_right_preconditioned).  Returns (x, info).
-
-  On a GPU the host side of an iteration (Givens rotations on the new Hessenberg column, the convergence test) runs ONE
-  ITERATION LATE (`lag`, default on for CUDA tensors): the column is normalised on the device, copied to page-locked
-  memory asynchronously, and read only after the NEXT iteration's preconditioner + operator + Gram-Schmidt have been
-  enqueued -- the device never waits for the host between sweeps.  The iterates, the stopping rule and the iteration
-  count are those of the plain loop; what the lag can cost is one discarded sweep when the solve converges earlier than
-  its own history predicts, so the loop turns synchronous as soon as the last observed reduction rate says the next
-  column may meet the tolerance (normally the last two or three iterations)."""
-  dev = b.device
-  n = b.numel()
-  if lag is None:
-    lag = dev.type == "cuda"
-  if ws is not None:        # captured iterations (_ArnoldiGraphs): static buffers, the operator applied inside the step
-    assert A is not None and sync is None and dev.type == "cuda" and ws.n == n and ws.m == restart
-    lag = True
-  if not lag or sync is not None:      # the fused Gram-Schmidt normalises on the device right away
-    ortho = None
-
-  def host_norm(v):
-    t = torch.linalg.vector_norm(v).reshape(1)
-    if sync is not None:
-      sync(t)
-    return float(t)
-
-  bnorm = host_norm(b)
-  y = torch.zeros(n, dtype=torch.float64, device=dev)
-  if x0 is not None:
-    b = b - (yield x0)
-    beta = host_norm(b)
-  else:
-    beta = bnorm
-  r = b.clone()
-  its = 0
-  res = beta / bnorm if bnorm > 0 else 0.0
-  history = []
-  wasted = 0
-  host_cols = ws.host_cols if ws is not None else (_pinned_columns(restart + 1, restart + 2) if lag else None)
-  events = [torch.cuda.Event(), torch.cuda.Event()] if lag else None
-  # the stream the iterations are enqueued on: looked up once (a solve does not change streams; the lookup is 4 us of the
-  # ~45 us of host time an iteration of a small deck costs)
-  ev_stream = torch.cuda.current_stream(dev) if lag else None
-  try:
-    while its < maxiter and res > tol:
-      m = min(restart, maxiter - its)
-      if ws is not None:
-        V, cols = ws.V, ws.cols
-      else:
-        V = torch.empty((m + 1, n), dtype=torch.float64, device=dev)
-        cols = torch.empty((m, m + 2), dtype=torch.float64, device=dev)    # row j = column j of H, then |w_j|
-      V[0] = r / beta
-      H = np.zeros((m + 1, m))
-      cs, sn = [0.0] * m, [0.0] * m          # plain Python floats: the rotations below are a scalar recurrence, and numpy
-      g = [0.0] * (m + 1)                    # scalars cost ~10x a float operation (it is host time between two sweeps)
-      g[0] = beta
-      k_used = 0
-      prev_res = None
-
-      def finish(j):
-        """Host side of iteration j: read its column, rotate, test.  True = stop after this column."""
-        nonlocal its, k_used, res, prev_res
-        if lag:
-          events[j & 1].synchronize()
-          col = host_cols[j, :j + 2].tolist()
-        else:
-          col = cols[j, :j + 2].tolist()                              # the one host transfer of the iteration
-        w_norm = col[-1]
-        last_norm[0] = w_norm
-        for i in range(j):                                           # previous rotations
-          t = cs[i] * col[i] + sn[i] * col[i + 1]
-          col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1]
-          col[i] = t
-        d = math.hypot(col[j], col[j + 1])
-        cs[j], sn[j] = (col[j] / d, col[j + 1] / d) if d > 0 else (1.0, 0.0)
-        col[j] = d
-        col[j + 1] = 0.0
-        H[:j + 2, j] = col
-        g[j + 1] = -sn[j] * g[j]
-        g[j] = cs[j] * g[j]
-        its += 1
-        k_used = j + 1
-        prev_res, res = res, abs(g[j + 1]) / bnorm
-        history.append(res)
-        return res <= tol or w_norm == 0 or not math.isfinite(w_norm)
-
-      def may_defer():
-        """Whether the pending column can wait until the next iteration has been enqueued: not when the last
-        observed reduction rate says it may already meet the tolerance."""
-        rate = min(1.0, res / prev_res) if prev_res else 1.0
-        return res * rate > 20.0 * tol
-
-      def orthogonalise(j, w):
-        """Two passes of classical Gram-Schmidt against V[0..j]; the new Hessenberg column and |w| go to cols[j]."""
-        Vj = V[:j + 1]
-        h = Vj @ w
-        w = torch.addmv(w, Vj.t(), h, alpha=-1.0)
-        h2 = Vj @ w
-        w = torch.addmv(w, Vj.t(), h2, alpha=-1.0)
-        torch.add(h, h2, out=cols[j, :j + 1])
-        torch.linalg.vector_norm(w, out=cols[j, j + 1])
-        return w
-
-      pending, stop, last_norm = None, False, [0.0]
-      for j in range(m):
-        if pending is not None and not may_defer():
-          stop, pending = finish(pending), None
-          if stop:
-            break
-        if ws is not None:
-          def device_side(j=j):
-            w = A(Minv(V[j]))
-            mapped = ws.col_mapped_ptr(j) if ortho is not None else 0
-            if ortho is not None:
-              if mapped:
-                ortho(V, j + 1, w, cols[j], V[j + 1], mapped)       # the kernel stores the column into host memory itself
-              else:
-                ortho(V, j + 1, w, cols[j], V[j + 1])
-            else:
-              torch.div(orthogonalise(j, w), cols[j, j + 1], out=V[j + 1])
-            if not mapped:
-              host_cols[j, :j + 2].copy_(cols[j, :j + 2], non_blocking=True)
-          ws.run(j, device_side, on_replay)
-        else:
-          w = yield Minv(V[j])
-          if ortho is not None:                                      # both passes, column, |w| and V[j + 1] in four launches
-            ortho(V, j + 1, w if w.is_contiguous() else w.contiguous(), cols[j], V[j + 1])
-          else:
-            w = orthogonalise(j, w)
-          if sync is not None:                                       # multi-rank: all ranks act on rank 0's numbers
-            sync(cols[j, :j + 2])
-        if lag:
-          if ws is None:
-            if ortho is None:
-              torch.div(w, cols[j, j + 1], out=V[j + 1])             # normalised on the device: no host value needed
-            host_cols[j, :j + 2].copy_(cols[j, :j + 2], non_blocking=True)
-          # fence on the stream the copy was enqueued on: the current stream of the VECTORS' device, which need not
-          # be the process's current device (a suspension built on cuda:1 while cuda:0 is current)
-          events[j & 1].record(ev_stream)
-          if pending is not None:
-            stop, pending = finish(pending), None
-            if stop:
-              wasted += 1                                            # iteration j was enqueued for nothing
-              break
-          pending = j
-        else:
-          stop = finish(j)
-          if last_norm[0] > 0:
-            torch.mul(w, 1.0 / last_norm[0], out=V[j + 1])
-          if stop:
-            break
-      if pending is not None and not stop:
-        finish(pending)
-      coef = np.linalg.solve(np.triu(H[:k_used, :k_used]), np.array(g[:k_used])) if k_used > 0 else np.zeros(0)
-      y = y + V[:k_used].t() @ torch.as_tensor(coef, device=dev)
-      if res > tol and its < maxiter:                                # restart: true residual
-        r = b - (yield Minv(y))
-        beta = host_norm(r)
-        res = beta / bnorm
-  finally:
-    if host_cols is not None and ws is None:
-      _pinned_pool.append(host_cols)
-  x = Minv(y)
-  if x0 is not None:
-    x = x + x0
-  return x, dict(iterations=its, residual=res, converged=bool(res <= tol), history=history, discarded_sweeps=wasted)
-
-
-def gmres_right_preconditioned(A, Minv, b, tol=1e-8, restart=60, maxiter=1000, x0=None, sync=None, lag=None, ws=None,
-                               on_replay=None, ortho=None):
-  """Solve A x = b with x = x0 + Minv y, GMRES(restart) on A.Minv (general_application_utils.py:608-627).
-  Stops when |b - A x| <= tol |b| (scipy `tol`, atol = 0) or after `maxiter` INNER iterations in total -- not restart
-  cycles: scipy (and the reference's call, maxiter=1000 with restart=60) counts cycles, i.e. up to 60 000 inner
-  iterations; the solves here converge in tens of iterations, so the cap only differs in how soon a diverging solve
-  gives up.
-  Arnoldi with two passes of classical Gram-Schmidt (one device GEMV each); Givens rotations on the host, on a GPU one
-  iteration behind the device (`lag`, see _gmres_steps; None = on for CUDA tensors).
-  x0: optional initial guess (the roller torque solve warm-starts from the previous step,
-  quaternion_integrator_rollers.py:961); the Krylov space is then built on the residual b - A x0."""
-  steps = _gmres_steps(Minv, b, tol, restart, maxiter, x0, sync, lag, ws=ws, A=A if ws is not None else None, on_replay=on_replay,
-                       ortho=ortho)
-  try:
-    request = next(steps)
-    while True:
-      request = steps.send(A(request))
-  except StopIteration as done:
-    return done.value
-
-
-def gmres_pair_right_preconditioned(A, A2, Minv, b_a, b_b, tol=1e-8, restart=60, maxiter=1000, sync=None, ortho=None):
-  """Two independent solves A x_a = b_a, A x_b = b_b advanced in lockstep: while both are running, each iteration
-  hands its two operator requests to A2(u, v) -> (A u, A v) -- one pass over the blob pairs with two vectors
-  (rmb_matvec2_device) instead of two.  Every solve sees exactly the iterates it would see alone.
-  Returns ((x_a, info_a), (x_b, info_b))."""
-  gens = [_gmres_steps(Minv, b, tol, restart, maxiter, None, sync, ortho=ortho) for b in (b_a, b_b)]
-  requests, results = [None, None], [None, None]
-  for k in (0, 1):
-    try:
-      requests[k] = next(gens[k])
-    except StopIteration as done:
-      results[k] = done.value
-  while results[0] is None or results[1] is None:
-    if results[0] is None and results[1] is None:
-      answers = A2(requests[0], requests[1])
-    else:
-      k = 0 if results[0] is None else 1
-      answers = [None, None]
-      answers[k] = A(requests[k])
-    for k in (0, 1):
-      if results[k] is None:
-        try:
-          requests[k] = gens[k].send(answers[k])
-        except StopIteration as done:
-          results[k] = done.value
-  return results[0], results[1]

@@ -23,13 +23,12 @@ stochastic_trapezoidal (:659).  The articulated schemes (:737-902) need the cons
 out of scope (constraints are not on the path).
 """
 import math
-import os
 
 import numpy as np
 import torch
 
 from .context import MobilityContext
-from .rigid import gmres_right_preconditioned
+from .krylov import gmres_right_preconditioned, switched_off
 from .stochastic import stochastic_forcing_lanczos
 
 
@@ -319,7 +318,7 @@ class RollersIntegrator(object):
 
   def _lanczos(self, mult, dim, z, dt, product=None):
     """factor M^{1/2} z; product ("tt" / "grand") names the operator `mult` applies when the library has it as ONE call."""
-    if (product is not None and self.native_lanczos is not False and os.environ.get("RMB_NATIVE_LANCZOS", "") != "0" and self.kT > 0.0
+    if (product is not None and self.native_lanczos is not False and not switched_off("RMB_NATIVE_LANCZOS") and self.kT > 0.0
         and self._ortho() is not None and not self.print_residual and self.Nblobs <= self.lanczos_native_max_blobs
         and (product == "tt" or self.domain != "in_plane")):
       zt = torch.as_tensor(z, dtype=torch.float64, device=self.device).reshape(-1).contiguous()

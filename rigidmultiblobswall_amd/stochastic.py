@@ -18,6 +18,8 @@ Differences in HOW:
 import numpy as np
 import torch
 
+from .krylov import drive, pair_server
+
 
 def _noise_coefficients(h_diag, h_sup, k, scale):
   """Small symmetric tridiagonal eigenproblem on the host (size k): noise = V[:k]^T coef."""
@@ -26,9 +28,37 @@ def _noise_coefficients(h_diag, h_sup, k, scale):
   return Q @ (np.sqrt(np.maximum(lam, 0.0)) * Q[0, :]) * scale
 
 
-def _plain_step(V, w, i, h_diag, h_sup, sync, v_norm, factor):
+class _LanczosHost(object):
+  """The host side of a Lanczos forcing, in one place: the tridiagonal coefficients h_ii and h_{i+1,i} as they arrive, the
+  coefficients of the noise estimate in the basis (the small eigenproblem), the reference's stopping rule
+  (stochastic_forcing.py:239-255: relative change of the estimate, here of its coefficient vector) and the lines of
+  `print_residual`."""
+
+  def __init__(self, scale, tolerance, print_residual):
+    self.scale, self.tolerance, self.print_residual = scale, tolerance, print_residual
+    self.h_diag, self.h_sup = [], []
+    self.coef = None                 # of the estimate after the last iteration seen: noise = V[:len(coef)]^T coef
+
+  def converged(self, i, h_ii, h_sup):
+    """Takes the two coefficients of iteration i (0, 1, ...); True when the estimate has stopped changing."""
+    self.h_diag.append(h_ii)
+    self.h_sup.append(h_sup)
+    coef_old, self.coef = self.coef, _noise_coefficients(self.h_diag, self.h_sup, i + 1, self.scale)
+    if i == 0:
+      return False
+    old = np.concatenate([coef_old, [0.0]])
+    old_norm = np.linalg.norm(old)
+    diff = np.linalg.norm(self.coef - old)
+    if self.print_residual:
+      if i == 1:
+        print('lanczos =  0 1')
+      print('lanczos = ', i, diff / old_norm)
+    return diff / max(old_norm, np.finfo(float).eps) < self.tolerance
+
+
+def _plain_step(V, w, i, h_sup, sync):
   """One Lanczos step as separate tensor operations (any device, any process group): three-term recurrence, the two
-  scalars to the host, the small eigenproblem, full re-orthogonalisation.  Returns (new basis vector, coef, k)."""
+  scalars to the host, full re-orthogonalisation.  Returns (new basis vector, h_ii, h_i+1,i)."""
   if i > 0:
     w = w - h_sup[i - 1] * V[i - 1]
   hd = torch.dot(w, V[i])
@@ -38,25 +68,21 @@ def _plain_step(V, w, i, h_diag, h_sup, sync, v_norm, factor):
   if sync is not None:           # multi-rank replicated loop: every rank acts on rank 0's coefficients
     sync(pair)
   hd_f, hs_f = (float(x) for x in pair.cpu())
-  h_diag.append(hd_f)
-  h_sup.append(hs_f)
   if hs_f > 0:
     w = w / hs_f
   else:
     w = torch.zeros_like(w)
     w[0] = 1.0
-  k = i + 1
-  coef = _noise_coefficients(h_diag, h_sup, k, v_norm * factor)
   # full re-orthogonalisation of the new basis vector (two classical Gram-Schmidt passes)
-  Vk = V[:k]
+  Vk = V[:i + 1]
   w = w - Vk.t() @ (Vk @ w)
   w = w - Vk.t() @ (Vk @ w)
-  return w, coef, k
+  return w, hd_f, hs_f
 
 
 def _lanczos_steps(factor, tolerance, max_iter, dim, z, print_residual, device, sync, ortho=None):
   """The Lanczos iteration as a coroutine: YIELDS every vector it needs the mobility applied to and receives the
-  product back, so that one driver can run a single forcing or advance two of them in lockstep on a two-vector
+  product back, so that krylov.drive can run a single forcing or advance two of them in lockstep on a two-vector
   product.  Returns (noise, iterations) before `L_mult`.
   ortho: optional fused orthogonalisation ortho(V, rows, w, col, v_next) (MobilityContext.krylov_orthogonalize_device:
   two classical Gram-Schmidt passes of w against V[:rows], col[:rows] = the coefficients, col[rows] = |w|,
@@ -70,9 +96,7 @@ def _lanczos_steps(factor, tolerance, max_iter, dim, z, print_residual, device, 
   col = torch.zeros(cap + 1, dtype=torch.float64, device=device) if ortho is not None else None
   v_norm = float(torch.linalg.norm(z))
   V[0] = z / v_norm
-  h_diag, h_sup = [], []
-  coef_old = None
-  coef = None
+  host = _LanczosHost(v_norm * factor, tolerance, print_residual)
   its = max_iter
   for i in range(max_iter + 1):
     w = (yield V[i]).reshape(-1)
@@ -85,36 +109,23 @@ def _lanczos_steps(factor, tolerance, max_iter, dim, z, print_residual, device, 
         col = torch.zeros(cap + 1, dtype=torch.float64, device=device)
     if ortho is not None and i + 1 <= 256:     # the fused step takes up to 256 basis vectors
       ortho(V, i + 1, w if w.is_contiguous() else w.contiguous(), col, V[i + 1])
-      hd_f, hs_f = col[i:i + 2].tolist()
-      broke = not (hs_f > 0 and np.isfinite(hs_f))
-      h_diag.append(hd_f)
-      h_sup.append(0.0 if broke else hs_f)
-      k = i + 1
-      coef = _noise_coefficients(h_diag, h_sup, k, v_norm * factor)
-      if broke:                    # exact breakdown (V[i + 1] holds 0 / 0): continue from e_0, orthogonalised, as the plain step does
+      h_ii, h_sup = col[i:i + 2].tolist()
+      if not (h_sup > 0 and np.isfinite(h_sup)):
+        # exact breakdown (V[i + 1] holds 0 / 0): continue from e_0, orthogonalised, as the plain step does
+        h_sup = 0.0
         w = torch.zeros(dim, dtype=torch.float64, device=device)
         w[0] = 1.0
-        Vk = V[:k]
+        Vk = V[:i + 1]
         w = w - Vk.t() @ (Vk @ w)
         w = w - Vk.t() @ (Vk @ w)
-        V[k] = w
+        V[i + 1] = w
     else:
-      w, coef, k = _plain_step(V, w, i, h_diag, h_sup, sync, v_norm, factor)
-      V[k] = w
-    if i > 0:
-      old = np.concatenate([coef_old, [0.0]])
-      old_norm = np.linalg.norm(old)
-      diff = np.linalg.norm(coef - old)
-      if print_residual:
-        if i == 1:
-          print('lanczos =  0 1')
-        print('lanczos = ', i, diff / old_norm)
-      if diff / max(old_norm, np.finfo(float).eps) < tolerance:
-        its = i
-        break
-    coef_old = coef
-  k = len(coef)
-  noise = V[:k].t() @ torch.as_tensor(coef, dtype=torch.float64, device=device)
+      V[i + 1], h_ii, h_sup = _plain_step(V, w, i, host.h_sup, sync)
+    if host.converged(i, h_ii, h_sup):
+      its = i
+      break
+  coef = host.coef
+  noise = V[:len(coef)].t() @ torch.as_tensor(coef, dtype=torch.float64, device=device)
   return noise, its
 
 
@@ -149,12 +160,7 @@ def stochastic_forcing_lanczos(factor=1.0, tolerance=1e-6, max_iter=1000, dim=No
     Mt = torch.as_tensor(mobility, dtype=torch.float64, device=device)
     mobility_mult = lambda v: Mt @ v  # noqa: E731
   steps = _lanczos_steps(factor, tolerance, max_iter, dim, z, print_residual, device, sync, ortho=ortho)
-  try:
-    request = next(steps)
-    while True:
-      request = steps.send(mobility_mult(request))
-  except StopIteration as done:
-    noise, its = done.value
+  noise, its = drive([steps], lambda requests: (mobility_mult(requests[0]),))[0]
   if L_mult is not None:
     noise = L_mult(noise).reshape(-1)
   return noise, its
@@ -167,23 +173,8 @@ def stochastic_forcing_lanczos_pair(factors, zs, mobility_mult, mobility_mult2, 
   forcing sees exactly the iterates it would see alone.  Returns ((noise_a, its_a), (noise_b, its_b))."""
   z0, dim, device = _prepare(zs[0], None, device, None)
   z1, _, _ = _prepare(zs[1], None, device, None)
-  gens = [_lanczos_steps(f, tolerance, max_iter, dim, z, print_residual, device, sync, ortho=ortho) for f, z in zip(factors, (z0, z1))]
-  requests, results = [None, None], [None, None]
-  for k in (0, 1):
-    requests[k] = next(gens[k])
-  while results[0] is None or results[1] is None:
-    if results[0] is None and results[1] is None:
-      answers = mobility_mult2(requests[0], requests[1])
-    else:
-      k = 0 if results[0] is None else 1
-      answers = [None, None]
-      answers[k] = mobility_mult(requests[k])
-    for k in (0, 1):
-      if results[k] is None:
-        try:
-          requests[k] = gens[k].send(answers[k])
-        except StopIteration as done:
-          results[k] = done.value
+  tasks = [_lanczos_steps(f, tolerance, max_iter, dim, z, print_residual, device, sync, ortho=ortho) for f, z in zip(factors, (z0, z1))]
+  results = drive(tasks, pair_server(mobility_mult, mobility_mult2))
   out = []
   for noise, its in results:
     out.append((L_mult(noise).reshape(-1) if L_mult is not None else noise, its))

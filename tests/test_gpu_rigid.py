@@ -239,7 +239,7 @@ def test_lagged_gmres_bookkeeping_equals_the_synchronous_loop():
   (general_application_utils.py:514-635) -- with restarts, with an initial guess, when the solve converges exactly at
   a restart boundary, and on a solve that converges in very few iterations (where the loop turns synchronous early)."""
   import torch
-  from rigidmultiblobswall_amd.rigid import gmres_right_preconditioned
+  from rigidmultiblobswall_amd.krylov import gmres_right_preconditioned
   dev = torch.device("cuda:0")
   rng = np.random.RandomState(5)
   n = 400
@@ -304,7 +304,7 @@ def _shell_suspension(nb, seed=5, **kw):
 
 
 def test_captured_arnoldi_iterations_equal_the_eager_loop():
-  """Small systems replay one captured hipGraph per Arnoldi iteration from the third solve on (rigid._ArnoldiGraphs).
+  """Small systems replay one captured hipGraph per Arnoldi iteration from the third solve on (krylov._ArnoldiGraphs).
   The iterates are those of the eager loop -- same kernels, same order: iteration counts and residual histories equal,
   solutions equal to rounding -- while bodies move, the preconditioner is rebuilt (K and the blocks are rewritten in
   place under the graphs), the right-hand side changes, with restarts and with an initial guess; a context option that
@@ -532,34 +532,37 @@ def test_native_loops_cover_the_references_42_blob_shells():
     nat.close(); ref.close()
 
 
-def test_native_lanczos_loop_equals_the_generic_one():
-  """RigidSuspension.stochastic_forcing three ways: the whole loop inside the library (rmb_rigid_lanczos_device: tridiagonal
-  eigen-solve and stopping rule in C, one iteration behind the device), one rmb_rigid_lanczos_step_device call per iteration
-  under the Python loop (coefficients through mapped memory), and the generic coroutine loop: same iteration count, same
-  noise to rounding, at several tolerances, with an iteration cap; a workspace with too few basis rows hands the forcing
-  back to the generic loop from either native path."""
+def test_native_lanczos_loop_equals_the_generic_one(capsys):
+  """RigidSuspension.stochastic_forcing two ways: the whole loop inside the library (rmb_rigid_lanczos_device: tridiagonal
+  eigen-solve and stopping rule in C, one iteration behind the device) and the generic coroutine loop: same iteration
+  count, same noise to rounding, at several tolerances; print_residual takes the generic loop (its lines are that loop's)
+  on a suspension that otherwise runs the library's; a workspace with too few basis rows hands the forcing back to the
+  generic loop."""
   import torch
   nat, _, _ = _shell_suspension(40)
-  stp, _, _ = _shell_suspension(40)
   gen, _, _ = _shell_suspension(40)
-  stp.native_lanczos_loop = False
   gen.native_lanczos = False
   rng = np.random.RandomState(11)
   try:
     for tol, factor in ((1e-3, 1.0), (1e-6, 0.37), (1e-10, 2.5)):
       z = torch.as_tensor(rng.randn(3 * nat.n_blobs), device="cuda:0")
-      m0, m1, calls = nat.matvec_count, stp.matvec_count, nat.lanczos_native_loop_calls
+      m0, calls = nat.matvec_count, nat.lanczos_native_loop_calls
       a, ia = nat.stochastic_forcing(z, factor, tol=tol)
-      s_, is_ = stp.stochastic_forcing(z, factor, tol=tol)
       b, ib = gen.stochastic_forcing(z, factor, tol=tol)
-      assert ia == ib == is_ and ia >= 2, (tol, ia, is_, ib)
+      assert ia == ib and ia >= 2, (tol, ia, ib)
       assert rel_err(a.cpu().numpy(), b.cpu().numpy()) < 1e-11, (tol, rel_err(a.cpu().numpy(), b.cpu().numpy()))
-      assert rel_err(s_.cpu().numpy(), b.cpu().numpy()) < 1e-11
-      assert rel_err(a.cpu().numpy(), s_.cpu().numpy()) < 1e-12            # same device work, eigen-solvers differ in rounding
       assert nat.matvec_count - m0 in (ia + 1, ia + 2)          # its + 1 products as the generic loop, + the discarded one
-      assert stp.matvec_count - m1 in (ia + 1, ia + 2)
-      assert nat.lanczos_native_loop_calls == calls + 1 and stp.lanczos_native_loop_calls == 0
-      assert stp._lanczos_ws is not None and getattr(nat, "_lanczos_ws", None) is None
+      assert nat.lanczos_native_loop_calls == calls + 1
+    # print_residual: the generic loop with the fused Gram-Schmidt, also where the library's loop is the default
+    z = torch.as_tensor(rng.randn(3 * nat.n_blobs), device="cuda:0")
+    b, ib = gen.stochastic_forcing(z, 0.37, tol=1e-6)
+    calls = nat.lanczos_native_loop_calls
+    capsys.readouterr()
+    p, ip = nat.stochastic_forcing(z, 0.37, tol=1e-6, print_residual=True)
+    lines = capsys.readouterr().out.splitlines()
+    assert nat.lanczos_native_loop_calls == calls and ip == ib
+    assert rel_err(p.cpu().numpy(), b.cpu().numpy()) < 1e-11, rel_err(p.cpu().numpy(), b.cpu().numpy())
+    assert lines[0] == "lanczos =  0 1" and len(lines) == 1 + ip and all(l.startswith("lanczos = ") for l in lines[1:]), lines
     # the defining identity on the library's loop alone: with w = L^-1 noise = (P^T M P)^{1/2} z, |w|^2 = (P z).M.(P z), P = L^-T
     z = torch.as_tensor(rng.randn(3 * nat.n_blobs), device="cuda:0")
     a, ia = nat.stochastic_forcing(z, 1.0, tol=1e-10)
@@ -577,16 +580,14 @@ def test_native_lanczos_loop_equals_the_generic_one():
         nat.ctx.set_option(key, 1)
       assert i0 == i1 == ia and rel_err(a0.cpu().numpy(), a1.cpu().numpy()) < 1e-13, keys
     assert rel_err(a0.cpu().numpy(), a.cpu().numpy()) < 1e-13
-    # too few basis rows: both native paths hand the forcing back to the generic loop
-    for s in (nat, stp):
-      s.lanczos_native_rows = 3
+    # too few basis rows: the native path hands the forcing back to the generic loop
+    nat.lanczos_native_rows = 3
     z = torch.as_tensor(rng.randn(3 * nat.n_blobs), device="cuda:0")
     a, ia = nat.stochastic_forcing(z, 1.0, tol=1e-8)
-    s_, is_ = stp.stochastic_forcing(z, 1.0, tol=1e-8)
     b, ib = gen.stochastic_forcing(z, 1.0, tol=1e-8)
-    assert ia == ib == is_ and ia > 3 and rel_err(a.cpu().numpy(), b.cpu().numpy()) < 1e-11 and rel_err(s_.cpu().numpy(), b.cpu().numpy()) < 1e-11
+    assert ia == ib and ia > 3 and rel_err(a.cpu().numpy(), b.cpu().numpy()) < 1e-11
   finally:
-    nat.close(); stp.close(); gen.close()
+    nat.close(); gen.close()
 
 
 def test_captured_arnoldi_iterations_with_mixed_shapes_and_prescribed_bodies():

@@ -48,7 +48,7 @@ def test_blob_positions_and_K_match_reference_body(g7):
 
 
 def test_gmres_driver_matches_direct_solve():
-  from rigidmultiblobswall_amd.rigid import gmres_right_preconditioned
+  from rigidmultiblobswall_amd.krylov import gmres_right_preconditioned
   rng = np.random.RandomState(1)
   n = 300
   A = np.eye(n) * 4 + rng.randn(n, n) * 0.1
@@ -148,7 +148,7 @@ def test_body_mobility_from_resistance_matches_pinv():
 def test_lockstep_gmres_pair_equals_two_solves():
   """gmres_pair_right_preconditioned: each of the two solves sees exactly the iterates it would see alone (same
   solution, same iteration count), whatever the other one does -- including one finishing long before the other."""
-  from rigidmultiblobswall_amd.rigid import gmres_right_preconditioned, gmres_pair_right_preconditioned
+  from rigidmultiblobswall_amd.krylov import gmres_right_preconditioned, gmres_pair_right_preconditioned
   rng = np.random.RandomState(21)
   n = 240
   M = np.eye(n) * 3 + rng.randn(n, n) * 0.12
@@ -177,3 +177,26 @@ def test_lockstep_gmres_pair_equals_two_solves():
     assert i1["iterations"] == j1["iterations"] and i2["iterations"] == j2["iterations"] <= 3
     assert calls["pair"] == j2["iterations"] and calls["single"] >= j1["iterations"] - j2["iterations"]
     assert float(torch.linalg.norm(A @ x1 - b1) / torch.linalg.norm(b1)) < 1e-9
+
+
+def test_drive_serves_every_round_of_lockstep_tasks_with_one_call():
+  """krylov.drive: each round collects the pending request of every running task, in task order, serves them with ONE
+  call and sends the answers back; a task that ends at its first `next` has its value recorded like any other; the
+  return values come back in task order."""
+  from rigidmultiblobswall_amd.krylov import drive
+
+  def task(name, requests):
+    seen = []
+    for k in range(requests):
+      seen.append((yield "%s%d" % (name, k)))
+    return name, seen
+
+  served = []
+
+  def serve(requests):
+    served.append(list(requests))
+    return [r.upper() for r in requests]
+  results = drive([task("a", 0), task("b", 2), task("c", 4)], serve)
+  assert served == [["b0", "c0"], ["b1", "c1"], ["c2"], ["c3"]]
+  assert results == [("a", []), ("b", ["B0", "B1"]), ("c", ["C0", "C1", "C2", "C3"])]
+  assert drive([], serve) == [] and len(served) == 4
