@@ -100,7 +100,9 @@ int rmb_ctx_destroy(rmb_ctx* ctx);
  * never stays bound to a stream it could not fence. */
 int rmb_ctx_set_stream(rmb_ctx* ctx, void* hip_stream);
 int rmb_ctx_release_stream(rmb_ctx* ctx);
-/* Options (unknown key -> RMB_ERR_ARG).  Defaults in [].
+/* Options (unknown key -> RMB_ERR_ARG).  Defaults in [].  The keys, what a set value is stored as (as given, clamped,
+ * 0 / 1, or refused) and the members behind them are ONE table: kOptions in csrc/rmb_context.hip, defaults in the option
+ * block of rmb_ctx (csrc/rmb_internal.h).
  *   "timing"          [0]  n >= 1 = bracket every n-th pair-sweep launch with HIP events (rmb_timing_collect); an
  *                          event pair serialises ~4-8 us around the launch, so throughput runs sample (n = 4)
  *   "symmetric"       [1]  1 = evaluate each unordered pair once and update both blobs (sym_kernels.h /
@@ -192,7 +194,7 @@ int rmb_ctx_release_stream(rmb_ctx* ctx);
  *   "skip_pairs"      [0]  diagnostics, results are WRONG: bit 0 = no pair arithmetic, bit 1 = no flush of the
  *                          per-wave LDS accumulators (tools/experiments/exp_prewarm.py prices the atomics with it)          */
 int rmb_ctx_set_option(rmb_ctx* ctx, const char* key, long value);
-/* Current value of an option (same keys); lets a caller switch one temporarily and restore what was there.  Read-only
+/* Current value of an option (same keys, same table); lets a caller switch one temporarily and restore what was there.  Read-only
  * key "last_path": the kernel family of the last product (0 one-sided sweep, 1 symmetric per wave, 2 deterministic
  * symmetric, 3 symmetric workgroup-cooperative, 4 symmetric with two target blobs per lane). */
 int rmb_ctx_get_option(rmb_ctx* ctx, const char* key, long* value);

@@ -26,6 +26,17 @@ int DevBuf::reserve(size_t bytes) {
   return 0;
 }
 
+int MappedBuf::reserve(size_t bytes, const hipStream_t* drain) {
+  if (bytes <= cap) return 0;
+  if (host && drain) RMB_HIP(hipStreamSynchronize(*drain));
+  release();
+  RMB_HIP(hipHostMalloc(&host, bytes, hipHostMallocMapped));
+  const hipError_t e = hipHostGetDevicePointer(&dev, host, 0);
+  if (e != hipSuccess) { release(); return fail(RMB_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e)); }
+  cap = bytes;
+  return 0;
+}
+
 int timing_begin(rmb_ctx* c, int* slot) {
   *slot = -1;
   if (!c->opt_timing) return 0;
@@ -82,6 +93,58 @@ int default_ctx(rmb_ctx** out) {
   return 0;
 }
 
+// ---- the option table ----------------------------------------------------------------------------------------------
+// Every settable key: the member of rmb_ctx behind it (rmb_internal.h lists them in this order, with defaults and the
+// measurements behind them) and what rmb_ctx_set_option does with a value; rmb_ctx_get_option walks it too.  It lives in
+// this translation unit because the diagnostics library differs from the release one in this object alone (RMB_DIAGNOSTICS).
+namespace {
+// what happens to a set value: stored as it comes; clamped into a..b (a floor: b = kNoCap); stored as 0 / 1; stored if it is
+// a, b or c and refused with `refusal` otherwise
+enum Norm { AS_GIVEN, CLAMP, BOOLEAN, ONE_OF };
+#ifdef RMB_DIAGNOSTICS
+constexpr long kDiagnosticsBuild = 1;
+#else
+constexpr long kDiagnosticsBuild = 0;
+#endif
+constexpr long kNoCap = 0x7fffffffffffffffL;
+struct Option {
+  const char* key;
+  long rmb_ctx::* field;
+  Norm norm = AS_GIVEN;
+  long a = 0, b = 0, c = 0;
+  const char* refusal = nullptr;
+  // Settable in the diagnostics build only (librmb_mobility_diag.so, tools/ only): what makes results WRONG ("skip_pairs") or changes which
+  // kernel runs ("wave_clock").  The release library refuses to set them (they read 0), so it cannot be talked into a silent wrong answer.
+  bool diagnostics = false;
+};
+const Option kOptions[] = {
+    {"chunks", &rmb_ctx::opt_chunks}, {"timing", &rmb_ctx::opt_timing}, {"symmetric", &rmb_ctx::opt_symmetric},
+    {"fused_symmetric", &rmb_ctx::opt_fused_symmetric}, {"symx_single", &rmb_ctx::opt_symx_single}, {"deterministic", &rmb_ctx::opt_deterministic},
+    {"det_workspace_mb", &rmb_ctx::opt_det_workspace_mb, CLAMP, 1, kNoCap},
+    {"sym_wps", &rmb_ctx::opt_sym_wps}, {"sym_pin", &rmb_ctx::opt_sym_pin},
+    {"free_surface", &rmb_ctx::opt_free_surface, BOOLEAN}, {"free_surface_rotation", &rmb_ctx::opt_free_surface_rotation, BOOLEAN},
+    {"precision", &rmb_ctx::opt_precision, ONE_OF, 32, 64, 64, "precision must be 32 or 64"},
+    {"force_precision", &rmb_ctx::opt_force_precision, ONE_OF, 0, 32, 64, "force_precision must be 0 (follow \"precision\"), 32 or 64"},
+    {"force_cull", &rmb_ctx::opt_force_cull, BOOLEAN}, {"force_sort", &rmb_ctx::opt_force_sort, BOOLEAN},
+    {"potential_resort", &rmb_ctx::opt_potential_resort, CLAMP, 1, kNoCap},      // (setting it also resets pot_sort_age)
+    {"sym_fine_steps", &rmb_ctx::opt_sym_fine_steps, CLAMP, 0, kNoCap},
+    {"sym_coop", &rmb_ctx::opt_sym_coop, ONE_OF, 0, 1, 2, "sym_coop must be 0 (never), 1 (launches below one resident round) or 2 (always)"},
+    {"sym_chunk_steps", &rmb_ctx::opt_sym_chunk_steps, CLAMP, 0, kNoCap}, {"sym_two_targets", &rmb_ctx::opt_sym_two_targets, CLAMP, 0, 2},
+    {"host_zero_copy_in", &rmb_ctx::opt_host_zero_copy_in, BOOLEAN}, {"gmres_fuse_pc", &rmb_ctx::opt_gmres_fuse_pc, BOOLEAN}, {"gmres_fuse_dots", &rmb_ctx::opt_gmres_fuse_dots, BOOLEAN},
+    {"krylov_low_sync", &rmb_ctx::opt_krylov_low_sync, BOOLEAN}, {"lanczos_fuse_finish", &rmb_ctx::opt_lanczos_fuse_finish, BOOLEAN},
+    {"host_zero_copy", &rmb_ctx::opt_host_zero_copy, CLAMP, 0, kNoCap},
+    {"sym_order", &rmb_ctx::opt_sym_order, BOOLEAN}, {"sym_xcd", &rmb_ctx::opt_sym_xcd, BOOLEAN},
+    {"sym_oversub", &rmb_ctx::opt_sym_oversub, CLAMP, 1, kNoCap}, {"sym_min_steps", &rmb_ctx::opt_sym_min_steps, CLAMP, 1, kNoCap},
+    {"wave_clock", &rmb_ctx::opt_wave_clock, AS_GIVEN, 0, 0, 0, nullptr, true}, {"skip_pairs", &rmb_ctx::opt_skip_pairs, AS_GIVEN, 0, 0, 0, nullptr, true},
+};
+
+const Option* find_option(const char* key) {
+  for (const Option& o : kOptions)
+    if (!strcmp(key, o.key)) return &o;
+  return nullptr;
+}
+}  // namespace
+
 }  // namespace rmbi
 
 using namespace rmbi;
@@ -124,7 +187,9 @@ int rmb_ctx_destroy(rmb_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   rmbi::gmres_release(c);
-  c->wave_clock.release(); c->pot_ws.release(); c->tile_bounds.release(); c->fpos.release(); c->fperm.release(); c->fsort_keys.release(); c->fsort_vals.release(); c->fsort_tmp.release(); c->fsort_box.release(); for (auto& b : c->st) b.release(); c->symbuf.release(); if (c->host_out) { (void)hipHostFree(c->host_out); c->host_out = nullptr; c->host_out_cap = 0; } if (c->host_in) { (void)hipHostFree(c->host_in); c->host_in = nullptr; c->host_in_cap = 0; } c->pos.release(); c->r_stage.release(); c->vec.release(); c->vec2.release(); c->out.release(); c->partial.release(); c->tmp3n.release(); c->det_ws.release(); c->krylov.release();
+  for_each_buffer(*c, [](DevBuf& b) { b.release(); });
+  c->host_out.release();
+  c->host_in.release();
   if (c->stream_switch) (void)hipEventDestroy(c->stream_switch);
   for (auto e : c->ev0) (void)hipEventDestroy(e);
   for (auto e : c->ev1) (void)hipEventDestroy(e);
@@ -166,100 +231,40 @@ int rmb_ctx_release_stream(rmb_ctx* c) {
 
 int rmb_ctx_set_option(rmb_ctx* c, const char* key, long value) {
   if (!c || !key) return fail(RMB_ERR_ARG, "null context / key");
-  if (!strcmp(key, "chunks")) { c->opt_chunks = value; return 0; }
-  if (!strcmp(key, "timing")) { c->opt_timing = value; return 0; }
-  if (!strcmp(key, "symmetric")) { c->opt_symmetric = value; return 0; }
-  if (!strcmp(key, "fused_symmetric")) { c->opt_fused_symmetric = value; return 0; }
-  if (!strcmp(key, "symx_single")) { c->opt_symx_single = value; return 0; }
-  if (!strcmp(key, "deterministic")) { c->opt_deterministic = value; return 0; }
-  if (!strcmp(key, "det_workspace_mb")) { c->opt_det_workspace_mb = value < 1 ? 1 : value; return 0; }
-  if (!strcmp(key, "sym_wps")) { c->opt_sym_wps = value; return 0; }
-#ifdef RMB_DIAGNOSTICS
-  // Diagnostics that make results WRONG ("skip_pairs") or change which kernel runs ("wave_clock") exist only in the
-  // diagnostics build of the library (librmb_mobility_diag.so, tools/ only): the release library's option table does
-  // not know them, so the boundary cannot be talked into a silent wrong answer.
-  if (!strcmp(key, "wave_clock")) { c->opt_wave_clock = value; return 0; }
-  if (!strcmp(key, "skip_pairs")) { c->opt_skip_pairs = value; return 0; }
-#else
-  if (!strcmp(key, "wave_clock") || !strcmp(key, "skip_pairs"))
+  const Option* o = find_option(key);
+  if (!o) return fail(RMB_ERR_ARG, std::string("unknown option: ") + key);
+  if (o->diagnostics && !kDiagnosticsBuild)
     return fail(RMB_ERR_ARG, std::string("option \"") + key + "\" exists only in the diagnostics build (librmb_mobility_diag.so, RMB_DIAGNOSTICS=1)");
-#endif
-  if (!strcmp(key, "sym_pin")) { c->opt_sym_pin = value; return 0; }
-  // takes effect at the next rmb_set_positions*: wall != 0 then loads a configuration above a stress-free surface
-  if (!strcmp(key, "free_surface")) { c->opt_free_surface = value ? 1 : 0; return 0; }
-  // takes effect at the next product: a free-surface configuration serves the rotational blocks of the mirror-image system
-  if (!strcmp(key, "free_surface_rotation")) { c->opt_free_surface_rotation = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "precision")) {
-    if (value != 32 && value != 64) return fail(RMB_ERR_ARG, "precision must be 32 or 64");
-    c->opt_precision = value;
-    return 0;
+  switch (o->norm) {
+    case AS_GIVEN: break;
+    case CLAMP: value = value < o->a ? o->a : (value > o->b ? o->b : value); break;
+    case BOOLEAN: value = value ? 1 : 0; break;
+    case ONE_OF: if (value != o->a && value != o->b && value != o->c) return fail(RMB_ERR_ARG, o->refusal); break;
   }
-  if (!strcmp(key, "force_cull")) { c->opt_force_cull = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "force_sort")) { c->opt_force_sort = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "potential_resort")) { c->opt_potential_resort = value < 1 ? 1 : value; c->pot_sort_age = -1; return 0; }
-  if (!strcmp(key, "force_precision")) {
-    if (value != 0 && value != 32 && value != 64) return fail(RMB_ERR_ARG, "force_precision must be 0 (follow \"precision\"), 32 or 64");
-    c->opt_force_precision = value;
-    return 0;
-  }
-  if (!strcmp(key, "sym_fine_steps")) { c->opt_sym_fine_steps = value < 0 ? 0 : value; return 0; }
-  if (!strcmp(key, "sym_coop")) {
-    if (value < 0 || value > 2) return fail(RMB_ERR_ARG, "sym_coop must be 0 (never), 1 (launches below one resident round) or 2 (always)");
-    c->opt_sym_coop = value;
-    return 0;
-  }
-  if (!strcmp(key, "sym_chunk_steps")) { c->opt_sym_chunk_steps = value < 0 ? 0 : value; return 0; }
-  if (!strcmp(key, "sym_two_targets")) { c->opt_sym_two_targets = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
-  if (!strcmp(key, "host_zero_copy_in")) { c->opt_host_zero_copy_in = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "gmres_fuse_pc")) { c->opt_gmres_fuse_pc = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "gmres_fuse_dots")) { c->opt_gmres_fuse_dots = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "krylov_low_sync")) { c->opt_krylov_low_sync = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "lanczos_fuse_finish")) { c->opt_lanczos_fuse_finish = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "host_zero_copy")) { c->opt_host_zero_copy = value < 0 ? 0 : value; return 0; }
-  if (!strcmp(key, "sym_order")) { c->opt_sym_order = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "sym_xcd")) { c->opt_sym_xcd = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "sym_oversub")) { c->opt_sym_oversub = value < 1 ? 1 : value; return 0; }
-  if (!strcmp(key, "sym_min_steps")) { c->opt_sym_min_steps = value < 1 ? 1 : value; return 0; }
-  return fail(RMB_ERR_ARG, std::string("unknown option: ") + key);
+  c->*(o->field) = value;
+  if (o->field == &rmb_ctx::opt_potential_resort) c->pot_sort_age = -1;      // the next evaluation builds the permutation
+  return 0;
 }
 
 int rmb_ctx_get_option(rmb_ctx* c, const char* key, long* value) {
   if (!c || !key || !value) return fail(RMB_ERR_ARG, "null context / key / value");
-  const struct { const char* name; const long* v; } table[] = {
-      {"chunks", &c->opt_chunks}, {"timing", &c->opt_timing}, {"symmetric", &c->opt_symmetric},
-      {"fused_symmetric", &c->opt_fused_symmetric}, {"symx_single", &c->opt_symx_single},
-      {"deterministic", &c->opt_deterministic}, {"det_workspace_mb", &c->opt_det_workspace_mb}, {"sym_wps", &c->opt_sym_wps},
-      {"wave_clock", &c->opt_wave_clock}, {"skip_pairs", &c->opt_skip_pairs}, {"sym_pin", &c->opt_sym_pin}, {"free_surface", &c->opt_free_surface},
-      {"free_surface_rotation", &c->opt_free_surface_rotation},
-      {"precision", &c->opt_precision}, {"force_precision", &c->opt_force_precision}, {"force_cull", &c->opt_force_cull}, {"force_sort", &c->opt_force_sort}, {"potential_resort", &c->opt_potential_resort}, {"sym_oversub", &c->opt_sym_oversub}, {"sym_fine_steps", &c->opt_sym_fine_steps}, {"sym_coop", &c->opt_sym_coop}, {"sym_order", &c->opt_sym_order}, {"host_zero_copy", &c->opt_host_zero_copy}, {"host_zero_copy_in", &c->opt_host_zero_copy_in}, {"gmres_fuse_pc", &c->opt_gmres_fuse_pc}, {"gmres_fuse_dots", &c->opt_gmres_fuse_dots}, {"krylov_low_sync", &c->opt_krylov_low_sync}, {"lanczos_fuse_finish", &c->opt_lanczos_fuse_finish}, {"sym_two_targets", &c->opt_sym_two_targets}, {"sym_chunk_steps", &c->opt_sym_chunk_steps}, {"sym_xcd", &c->opt_sym_xcd},
-      {"sym_min_steps", &c->opt_sym_min_steps}};
   // read-only: which kernel family the last product ran on (0 one-sided sweep, 1 symmetric per-wave, 2 deterministic
   // symmetric, 3 symmetric workgroup-cooperative)
   if (!strcmp(key, "last_path")) { *value = c->last_path; return 0; }
-  if (!strcmp(key, "diagnostics_build")) {
-#ifdef RMB_DIAGNOSTICS
-    *value = 1;
-#else
-    *value = 0;
-#endif
-    return 0;
-  }
-  // read-only: a hash of the addresses of every device buffer the library owns for this context.  A captured hipGraph
-  // of device-path calls holds those addresses by value; it stays valid exactly while this number is unchanged (a
+  if (!strcmp(key, "diagnostics_build")) { *value = kDiagnosticsBuild; return 0; }
+  // read-only: a hash of the addresses of every device buffer the library owns for this context (CtxBuffers).  A captured
+  // hipGraph of device-path calls holds those addresses by value; it stays valid exactly while this number is unchanged (a
   // buffer that grows is freed and reallocated, DevBuf::reserve).
   if (!strcmp(key, "buffers_signature")) {
     unsigned long long h = 1469598103934665603ull;
-    auto mix = [&h](const rmbi::DevBuf& b) { h = (h ^ (unsigned long long)(uintptr_t)b.p) * 1099511628211ull; };
-    mix(c->pos); mix(c->r_stage); mix(c->vec); mix(c->vec2); mix(c->out); mix(c->partial); mix(c->tmp3n); mix(c->tile_bounds);
-    mix(c->fpos); mix(c->fperm); mix(c->fsort_keys); mix(c->fsort_vals); mix(c->fsort_tmp); mix(c->fsort_box); mix(c->det_ws);
-    for (const auto& b : c->st) mix(b);
-    mix(c->wave_clock); mix(c->pot_ws); mix(c->krylov); mix(c->symbuf);
+    for_each_buffer(*c, [&h](const DevBuf& b) { h = (h ^ (unsigned long long)(uintptr_t)b.p) * 1099511628211ull; });
     *value = (long)(h >> 1);
     return 0;
   }
-  for (const auto& e : table)
-    if (!strcmp(key, e.name)) { *value = *e.v; return 0; }
-  return fail(RMB_ERR_ARG, std::string("unknown option: ") + key);
+  const Option* o = find_option(key);
+  if (!o) return fail(RMB_ERR_ARG, std::string("unknown option: ") + key);
+  *value = c->*(o->field);
+  return 0;
 }
 
 int rmb_timing_collect(rmb_ctx* c, double* ms, int max_n) {

@@ -9,6 +9,13 @@
 namespace rmbi {
 
 namespace {
+// the argument checks most products open with
+int check_eta(double eta) { return eta > 0.0 ? 0 : fail(RMB_ERR_ARG, "eta must be positive"); }
+int check_shard(long shard, long nshards, const char* msg = "bad shard / nshards") {
+  return nshards >= 1 && shard >= 0 && shard < nshards ? 0 : fail(RMB_ERR_ARG, msg);
+}
+bool is_periodic(const rmb_ctx* c) { return c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0; }
+
 // What the rotational products above a free surface (option "free_surface_rotation") do not have: an in-plane variant, the
 // fp32 twins, pseudo-periodic images along z.  Refused by name -- a missing variant must not run something else.
 int free_surface_rotation_ok(const rmb_ctx* c, int in_plane) {
@@ -59,10 +66,9 @@ int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, cons
   if (n_tgt == 0) return 0;
   if (!v || !out) return fail(RMB_ERR_ARG, "null vector / output pointer");
   if (rmb::kind_has_torque(kind) && !v2) return fail(RMB_ERR_ARG, "RMB_TT_TR needs vec2 (torque)");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
+  if (int rc = check_eta(eta)) return rc;
   RMB_HIP(hipSetDevice(c->device));
 
-  const bool periodic = c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0;
   c->last_path = 0;
   if (sym_applies(c)) {
     // every product of the surface is a symmetric operator: each unordered pair once, applied to both blobs
@@ -75,7 +81,7 @@ int matvec_device_impl(rmb_ctx* c, int kind, int in_plane, const double* v, cons
     }
     if (kind <= rmb::KIND_RR) {
       // tr / rt / rr in single precision run on the generic skeleton's fp32 twin (tt has its own kernel in sym_device)
-      const bool x32 = c->opt_precision == 32 && kind != rmb::KIND_TT && !periodic;
+      const bool x32 = c->opt_precision == 32 && kind != rmb::KIND_TT && !is_periodic(c);
       if (in_plane || c->opt_symx_single || x32) return symx_device(c, SX_TT + kind, in, outs, eta, in_plane, 0, 1);
       return sym_device(c, kind, v, eta, out);
     }
@@ -102,9 +108,8 @@ int force_device_impl(rmb_ctx* c, double eps, double b, double blob_radius, doub
   if (n_tgt == 0) return 0;
   if (!out) return fail(RMB_ERR_ARG, "null output pointer");
   if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
-  if (nshards < 1 || shard < 0 || shard >= nshards) return fail(RMB_ERR_ARG, "bad shard / nshards");
+  if (int rc = check_shard(shard, nshards)) return rc;
   RMB_HIP(hipSetDevice(c->device));
-  const bool periodic = c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0;
   c->last_path = 0;
   // symmetric path: each unordered pair once (F_ji = -F_ij); its flushes are atomics, so both deterministic modes
   // take the one-sided sweep
@@ -132,10 +137,10 @@ int matvec_pairshard_impl(rmb_ctx* c, int kind, int in_plane, const double* v, d
     return fail(RMB_ERR_STATE, "RMB_TT_FREE_SURFACE uses raw heights: call rmb_set_positions with wall = 0");
   if (in_plane && kind != rmb::KIND_TT_FREE)
     return fail(RMB_ERR_ARG, "pair shards with in_plane: use rmb_matvec_op_pairshard_device (RMB_OP_*_MULTI) for RMB_TT / TR / RT / RR");
-  if (nshards < 1 || shard < 0 || shard >= nshards) return fail(RMB_ERR_ARG, "bad shard / nshards");
+  if (int rc = check_shard(shard, nshards)) return rc;
   if (c->n == 0) return 0;
   if (!v || !out) return fail(RMB_ERR_ARG, "null vector / output pointer");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
+  if (int rc = check_eta(eta)) return rc;
   RMB_HIP(hipSetDevice(c->device));
   c->last_path = 1;
   const int sx = free_kind ? free_surface_sx(kind) : SX_TT + kind;
@@ -151,8 +156,8 @@ int matvec_op_impl(rmb_ctx* c, int op, int in_plane, int n_in, const double* con
                    double eta, long shard, long nshards) {
   if (int rc = check_ready(c)) return rc;
   if (!in || !out) return fail(RMB_ERR_ARG, "null vector / output list");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
-  if (nshards < 1 || shard < 0 || shard >= nshards) return fail(RMB_ERR_ARG, "bad shard / nshards");
+  if (int rc = check_eta(eta)) return rc;
+  if (int rc = check_shard(shard, nshards)) return rc;
   int want_in = 0, want_out = 0, sx = -1, multi_kind = rmb::KIND_TT;
   switch (op) {
     case RMB_OP_VELOCITY_FROM_FORCE_TORQUE: want_in = 2; want_out = 1; sx = SX_FUSED; break;
@@ -213,13 +218,19 @@ int matvec_op_impl(rmb_ctx* c, int op, int in_plane, int n_in, const double* con
 }
 
 namespace {
-// host arrays -> staging buffers of the default context; returns device pointers in dev[]
+// Host staging of the synchronous entry points.  aux_stage: host arrays -> the scratch buffers st[slot[k]] (enqueued; an empty
+// array still gets a valid address), device pointers in dev[]; download: device -> host, and wait.
 int aux_stage(rmb_ctx* c, int n, const double* const* host, const size_t* bytes, const int* slot, const double** dev) {
   for (int k = 0; k < n; ++k) {
     if (int rc = c->st[slot[k]].reserve(bytes[k] ? bytes[k] : sizeof(double))) return rc;
     if (bytes[k]) RMB_HIP(hipMemcpyAsync(c->st[slot[k]].p, host[k], bytes[k], hipMemcpyHostToDevice, c->stream));
     dev[k] = (const double*)c->st[slot[k]].p;
   }
+  return 0;
+}
+int download(rmb_ctx* c, void* host, const void* dev, size_t bytes) {
+  RMB_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  RMB_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -293,8 +304,8 @@ int rmb_matvec2_pairshard_device(rmb_ctx* c, int kind, const double* vec_a, cons
   if (kind != rmb::KIND_TT) return fail(RMB_ERR_ARG, "two-vector products exist for RMB_TT only");
   if (c->free_surface) return fail(RMB_ERR_STATE, "free-surface context: no two-vector pass above a free surface (use rmb_matvec_device per vector)");
   if (!vec_a || !vec_b || !out_a || !out_b) return fail(RMB_ERR_ARG, "null vector / output pointer");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
-  if (nshards < 1 || shard < 0 || shard >= nshards) return fail(RMB_ERR_ARG, "bad shard");
+  if (int rc = check_eta(eta)) return rc;
+  if (int rc = check_shard(shard, nshards, "bad shard")) return rc;
   RMB_HIP(hipSetDevice(c->device));
   if (!sym_applies(c) && nshards == 1) {
     if (int rc = matvec_device_impl(c, kind, 0, vec_a, nullptr, eta, out_a)) return rc;
@@ -302,8 +313,7 @@ int rmb_matvec2_pairshard_device(rmb_ctx* c, int kind, const double* vec_a, cons
   }
   // a pair shard (nshards > 1) always runs the symmetric kernel, whatever n: it is the only kernel that can
   // evaluate a slice of the unordered pairs (rmb_matvec_pairshard_device does the same)
-  const bool periodic = c->L[0] > 0 || c->L[1] > 0 || c->L[2] > 0;
-  const bool x32 = c->opt_precision == 32 && !periodic;     // the generic skeleton has the single-precision twin
+  const bool x32 = c->opt_precision == 32 && !is_periodic(c);     // the generic skeleton has the single-precision twin
   if (c->opt_symx_single || x32 || c->opt_deterministic == 2) {
     const double* in[2] = {vec_a, vec_b};
     double* outs[2] = {out_a, out_b};
@@ -343,7 +353,7 @@ int rmb_body_mobility_dense_device(rmb_ctx* c, const long* first_blob_dev, long 
   if (n_bodies < 0 || n_b < 1) return fail(RMB_ERR_ARG, "bad n_bodies / blobs per body");
   if (n_bodies == 0) return 0;
   if (!first_blob_dev || !out_dev) return fail(RMB_ERR_ARG, "null pointer");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
+  if (int rc = check_eta(eta)) return rc;
   // Periodic contexts are accepted: a body's own block never includes images (the reference's per-body
   // b.calc_mobility_blobs, body/body.py:186-191, has no periodic_length either).
   RMB_HIP(hipSetDevice(c->device));
@@ -367,16 +377,13 @@ int rmb_matvec(rmb_ctx* c, int kind, int in_plane, const double* v, const double
   // the product's own queue, instead of a host-to-device copy command on the copy queue.
   const bool pull_in = c->opt_host_zero_copy_in && c->opt_host_zero_copy > 0 && vb <= (size_t)c->opt_host_zero_copy && n >= 128;
   const int n_vec = kind == rmb::KIND_TT_TR ? 2 : 1;
-  if (pull_in && (size_t)n_vec * vb > c->host_in_cap) {
-    if (c->host_in) { (void)hipHostFree(c->host_in); c->host_in = nullptr; c->host_in_cap = 0; }
-    const size_t want = 2 * (vb + vb / 8) + 4096;
-    RMB_HIP(hipHostMalloc(&c->host_in, want, hipHostMallocMapped));
-    RMB_HIP(hipHostGetDevicePointer((void**)&c->host_in_dev, c->host_in, 0));
-    c->host_in_cap = want;
-  }
+  // (growth of host_in / host_out below frees without a wait: the pull kernels and the finalize kernel that used them belong
+  //  to an earlier rmb_matvec, and every rmb_matvec ends with a wait for its stream)
+  if (pull_in && (size_t)n_vec * vb > c->host_in.cap)       // then: room for two vectors and an eighth more
+    if (int rc = c->host_in.reserve(2 * (vb + vb / 8) + 4096)) return rc;
   if (pull_in) {
-    memcpy(c->host_in, v, vb);
-    if (int rc = pull_mapped(c, (double*)c->vec.p, c->host_in_dev, 3 * n)) return rc;
+    memcpy(c->host_in.host, v, vb);
+    if (int rc = pull_mapped(c, (double*)c->vec.p, (const double*)c->host_in.dev, 3 * n)) return rc;
   } else {
     RMB_HIP(hipMemcpyAsync(c->vec.p, v, vb, hipMemcpyHostToDevice, c->stream));
   }
@@ -384,8 +391,8 @@ int rmb_matvec(rmb_ctx* c, int kind, int in_plane, const double* v, const double
   if (kind == rmb::KIND_TT_TR) {
     if (int rc = c->vec2.reserve(vb)) return rc;
     if (pull_in) {
-      memcpy((char*)c->host_in + vb, v2, vb);
-      if (int rc = pull_mapped(c, (double*)c->vec2.p, c->host_in_dev + 3 * n, 3 * n)) return rc;
+      memcpy((char*)c->host_in.host + vb, v2, vb);
+      if (int rc = pull_mapped(c, (double*)c->vec2.p, (const double*)c->host_in.dev + 3 * n, 3 * n)) return rc;
     } else {
       RMB_HIP(hipMemcpyAsync(c->vec2.p, v2, vb, hipMemcpyHostToDevice, c->stream));
     }
@@ -398,22 +405,16 @@ int rmb_matvec(rmb_ctx* c, int kind, int in_plane, const double* v, const double
   // Larger results take the copy command (mapped stores lose from ~1e5 blobs on); so does the one-sided sweep
   // ("deterministic" = 1), whose final stores are 8 bytes at a stride of 24.
   const bool zero_copy = c->opt_host_zero_copy > 0 && ob <= (size_t)c->opt_host_zero_copy && c->opt_deterministic != 1 && n >= 128;
-  if (zero_copy && ob > c->host_out_cap) {
-    if (c->host_out) { (void)hipHostFree(c->host_out); c->host_out = nullptr; c->host_out_cap = 0; }
-    const size_t want = ob + ob / 8 + 4096;
-    RMB_HIP(hipHostMalloc(&c->host_out, want, hipHostMallocMapped));
-    RMB_HIP(hipHostGetDevicePointer((void**)&c->host_out_dev, c->host_out, 0));
-    c->host_out_cap = want;
-  }
+  if (zero_copy && ob > c->host_out.cap)
+    if (int rc = c->host_out.reserve(ob + ob / 8 + 4096)) return rc;
   const auto t1 = std::chrono::steady_clock::now();
-  if (int rc = matvec_device_impl(c, kind, in_plane, (const double*)c->vec.p, v2d, eta, zero_copy ? c->host_out_dev : (double*)c->out.p)) return rc;
+  if (int rc = matvec_device_impl(c, kind, in_plane, (const double*)c->vec.p, v2d, eta, (double*)(zero_copy ? c->host_out.dev : c->out.p))) return rc;
   const auto t2 = std::chrono::steady_clock::now();
   if (zero_copy) {
     RMB_HIP(hipStreamSynchronize(c->stream));
-    memcpy(out, c->host_out, ob);
-  } else {
-    RMB_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    RMB_HIP(hipStreamSynchronize(c->stream));
+    memcpy(out, c->host_out.host, ob);
+  } else if (int rc = download(c, out, c->out.p, ob)) {
+    return rc;
   }
   const auto t3 = std::chrono::steady_clock::now();
   const auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -463,13 +464,12 @@ int rmb_blob_blob_force_radii(rmb_ctx* c, const double* radii, double eps, doubl
   if (!out || !radii) return fail(RMB_ERR_ARG, "null pointer");
   RMB_HIP(hipSetDevice(c->device));
   const size_t ob = (size_t)3 * n_tgt * sizeof(double), rb = (size_t)c->n * sizeof(double);
+  const double* radii_dev;
+  const int slot = 3;      // (the radii slot of rmb_mobility_source_target)
   if (int rc = c->out.reserve(ob)) return rc;
-  if (int rc = c->vec2.reserve(rb)) return rc;
-  RMB_HIP(hipMemcpyAsync(c->vec2.p, radii, rb, hipMemcpyHostToDevice, c->stream));
-  if (int rc = force_device_impl(c, eps, b, 0.0, (double*)c->out.p, (const double*)c->vec2.p)) return rc;
-  RMB_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-  RMB_HIP(hipStreamSynchronize(c->stream));
-  return 0;
+  if (int rc = aux_stage(c, 1, &radii, &rb, &slot, &radii_dev)) return rc;
+  if (int rc = force_device_impl(c, eps, b, 0.0, (double*)c->out.p, radii_dev)) return rc;
+  return download(c, out, c->out.p, ob);
 }
 
 int rmb_blob_blob_force(rmb_ctx* c, double eps, double b, double blob_radius, double* out) {
@@ -481,9 +481,7 @@ int rmb_blob_blob_force(rmb_ctx* c, double eps, double b, double blob_radius, do
   const size_t ob = (size_t)3 * n_tgt * sizeof(double);
   if (int rc = c->out.reserve(ob)) return rc;
   if (int rc = force_device_impl(c, eps, b, blob_radius, (double*)c->out.p)) return rc;
-  RMB_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-  RMB_HIP(hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->out.p, ob);
 }
 
 int rmb_mobility_source_target_device(rmb_ctx* c, long ns, const double* src_dev, const double* rad_s_dev, long nt,
@@ -494,7 +492,7 @@ int rmb_mobility_source_target_device(rmb_ctx* c, long ns, const double* src_dev
   if (nt == 0) return 0;
   if (!out_dev || !tgt_dev || !rad_t_dev) return fail(RMB_ERR_ARG, "null target pointer");
   if (ns > 0 && (!src_dev || !rad_s_dev || !force_dev)) return fail(RMB_ERR_ARG, "null source pointer");
-  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
+  if (int rc = check_eta(eta)) return rc;
   RMB_HIP(hipSetDevice(c->device));
   if (ns == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, (size_t)3 * nt * sizeof(double), c->stream)); return 0; }
   if (src_dev == tgt_dev && rad_s_dev == rad_t_dev && ns == nt && ns >= 128 && (wall == 0 || wall == 1) &&
@@ -526,33 +524,21 @@ int rmb_mobility_source_target(long ns, const double* src, const double* rad_s, 
   if (nt == 0) return 0;
   if (!out || !tgt || !rad_t || (ns > 0 && (!src || !rad_s || !force))) return fail(RMB_ERR_ARG, "null pointer");
   RMB_HIP(hipSetDevice(c->device));
-  const size_t bs3 = (size_t)3 * (ns > 0 ? ns : 1) * sizeof(double), bt3 = (size_t)3 * nt * sizeof(double);
-  const size_t bs1 = (size_t)(ns > 0 ? ns : 1) * sizeof(double), bt1 = (size_t)nt * sizeof(double);
-  if (int rc = c->st[2].reserve(bs3)) return rc;   // src
-  if (int rc = c->st[3].reserve(bs1)) return rc;   // rad_s
-  if (int rc = c->st[4].reserve(bt3)) return rc;   // tgt
-  if (int rc = c->st[5].reserve(bt1)) return rc;   // rad_t
-  if (int rc = c->st[6].reserve(bs3)) return rc;   // force
+  const size_t bs3 = (size_t)3 * ns * sizeof(double), bt3 = (size_t)3 * nt * sizeof(double);
+  const double* host[5] = {src, rad_s, force, tgt, rad_t};
+  const size_t bytes[5] = {bs3, (size_t)ns * sizeof(double), bs3, bt3, (size_t)nt * sizeof(double)};
+  const int slot[5] = {2, 3, 6, 4, 5};
+  const double* dev[5];
+  if (int rc = aux_stage(c, 5, host, bytes, slot, dev)) return rc;
   if (int rc = c->st[7].reserve(bt3)) return rc;   // out
-  if (ns > 0) {
-    RMB_HIP(hipMemcpyAsync(c->st[2].p, src, (size_t)3 * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    RMB_HIP(hipMemcpyAsync(c->st[3].p, rad_s, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    RMB_HIP(hipMemcpyAsync(c->st[6].p, force, (size_t)3 * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  RMB_HIP(hipMemcpyAsync(c->st[4].p, tgt, bt3, hipMemcpyHostToDevice, c->stream));
-  RMB_HIP(hipMemcpyAsync(c->st[5].p, rad_t, bt1, hipMemcpyHostToDevice, c->stream));
   // sources == targets (same arrays, or equal contents): hand the device entry the SAME pointers, which selects its
   // symmetric path
   const bool same = ns == nt && ns > 0 && (src == tgt || !memcmp(src, tgt, (size_t)3 * ns * sizeof(double))) &&
                     (rad_s == rad_t || !memcmp(rad_s, rad_t, (size_t)ns * sizeof(double)));
-  const double* tgt_d = same ? (const double*)c->st[2].p : (const double*)c->st[4].p;
-  const double* radt_d = same ? (const double*)c->st[3].p : (const double*)c->st[5].p;
-  if (int rc = rmb_mobility_source_target_device(c, ns, (const double*)c->st[2].p, (const double*)c->st[3].p, nt, tgt_d, radt_d,
-                                                 (const double*)c->st[6].p, eta, L, wall, (double*)c->st[7].p))
+  if (int rc = rmb_mobility_source_target_device(c, ns, dev[0], dev[1], nt, same ? dev[0] : dev[3], same ? dev[1] : dev[4], dev[2], eta,
+                                                 L, wall, (double*)c->st[7].p))
     return rc;
-  RMB_HIP(hipMemcpyAsync(out, c->st[7].p, bt3, hipMemcpyDeviceToHost, c->stream));
-  RMB_HIP(hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->st[7].p, bt3);
 }
 
 int rmb_pressure_stokeslet_device(rmb_ctx* c, long ns, const double* src_dev, long nt, const double* tgt_dev,
@@ -601,9 +587,7 @@ int rmb_pressure_stokeslet(long ns, const double* src, long nt, const double* tg
   if (int rc = aux_stage(c, 3, host, bytes, slot, dev)) return rc;
   if (int rc = c->st[7].reserve((size_t)nt * sizeof(double))) return rc;
   if (int rc = rmb_pressure_stokeslet_device(c, ns, dev[0], nt, dev[1], dev[2], L, wall, (double*)c->st[7].p)) return rc;
-  RMB_HIP(hipMemcpyAsync(out, c->st[7].p, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  RMB_HIP(hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->st[7].p, (size_t)nt * sizeof(double));
 }
 
 int rmb_double_layer(long ns, const double* src, long nt, const double* tgt, const double* normals, const double* vector,
@@ -624,9 +608,7 @@ int rmb_double_layer(long ns, const double* src, long nt, const double* tgt, con
   if (int rc = c->st[7].reserve(b3t)) return rc;
   if (int rc = rmb_double_layer_device(c, ns, dev[0], nt, dev[1], dev[2], dev[3], dev[4], wall, blob_radius, (double*)c->st[7].p))
     return rc;
-  RMB_HIP(hipMemcpyAsync(out, c->st[7].p, b3t, hipMemcpyDeviceToHost, c->stream));
-  RMB_HIP(hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->st[7].p, b3t);
 }
 
 int rmb_mobility_oneshot(int kind, int wall, int in_plane, long n, const double* r, const double* vec,

@@ -171,37 +171,71 @@ bool noise_coefficients(long k, const double* h_diag, const double* h_sup, doubl
   return true;
 }
 
-struct Mapped {
-  void* host = nullptr;
-  void* dev = nullptr;
-  size_t cap = 0;
-};
-
-}  // namespace
-}  // namespace rmbi
-
-using namespace rmbi;
-
-// Per-context workspace of the native GMRES: device vectors in one DevBuf, mapped host memory for the Hessenberg columns, the
-// back-substitution coefficients and one scalar.  Grows, never shrinks; freed with the context (rmb_ctx_destroy calls
-// rmb_gmres_release).
+// Per-context workspace of the native loops (GMRES and the Lanczos forcings share it): device vectors in one DevBuf, mapped host
+// memory for the coefficient rows, the combination coefficients and one scalar.  Grows, never shrinks; freed with the context
+// (rmb_ctx_destroy calls gmres_release).
 struct rmb_gmres_ws {
   DevBuf dev;
-  Mapped mapped;
+  MappedBuf mapped;
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
-namespace rmbi {
+// Coefficients of one linear combination of basis rows: the size of vec_lincomb_kernel's LDS copy (its cl[256]) and of the
+// hcoef region below.  A GMRES cycle combines up to `restart` rows of a basis of restart + 1, the Lanczos loops up to
+// max_rows of max_rows + 1, so the entries refuse restart > kCoefMax - 1 and max_rows > kCoefMax - 2 (their texts say 255 / 254).
+constexpr long kCoefMax = 256;
+
+// The workspace as one loop sees it: `rows` Krylov steps at most on vectors of `dim` doubles, `n_work` work vectors.
+struct KrylovWs {
+  long dim;
+  double* V;                     // basis, rows + 1 vectors (leading dimension dim)
+  double* x;                     // the work vectors, one after the other: work(k)
+  double* cols;                  // [rows][col_row] coefficient rows on the device (Hessenberg columns / Lanczos h_ii, h_{i+1,i})
+  size_t col_row;                // rows + 2
+  double *hcols, *hcols_dev;     // the same rows in mapped host memory: the host's address and the kernels'
+  double *hcoef, *hcoef_dev;     // kCoefMax combination coefficients (the host writes, vec_lincomb_kernel reads)
+  double *hscal, *hscal_dev;     // one scalar (a norm)
+  hipEvent_t* ev;                // two events, steps alternate
+  double* work(int k) const { return x + (size_t)k * dim; }
+};
+
+// The one place that sizes and carves the workspace.  Mapped part: [rows x col_row | kCoefMax | 8], so where hcoef lies depends
+// on `rows`.  Both loops end on a vec_lincomb_kernel launch that reads hcoef and do not wait for it (notes there); that holds
+// across calls with different `rows` because each loop waits for a norm before its host side writes anything here, and
+// growth of the mapped memory drains the stream before the old memory is freed.
+int krylov_workspace(rmb_ctx* c, long rows, long dim, int n_work, KrylovWs* w) {
+  if (!c->gmres_ws) c->gmres_ws = new rmb_gmres_ws();
+  rmb_gmres_ws* ws = (rmb_gmres_ws*)c->gmres_ws;
+  const size_t col_row = (size_t)(rows + 2), n_cols = (size_t)rows * col_row;
+  if (int rc = ws->dev.reserve(((size_t)(rows + 1 + n_work) * dim + n_cols) * sizeof(double))) return rc;
+  if (int rc = ws->mapped.reserve((n_cols + kCoefMax + 8) * sizeof(double), &c->stream)) return rc;
+  for (auto& e : ws->ev) if (!e) RMB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  w->dim = dim;
+  w->V = (double*)ws->dev.p;
+  w->x = w->V + (size_t)(rows + 1) * dim;
+  w->cols = w->x + (size_t)n_work * dim;
+  w->col_row = col_row;
+  w->hcols = (double*)ws->mapped.host;   w->hcols_dev = (double*)ws->mapped.dev;
+  w->hcoef = w->hcols + n_cols;          w->hcoef_dev = w->hcols_dev + n_cols;
+  w->hscal = w->hcoef + kCoefMax;        w->hscal_dev = w->hcoef_dev + kCoefMax;
+  w->ev = ws->ev;
+  return 0;
+}
+
+}  // namespace
+
 void gmres_release(rmb_ctx* c) {
   rmb_gmres_ws* w = (rmb_gmres_ws*)c->gmres_ws;
   if (!w) return;
   w->dev.release();
-  if (w->mapped.host) (void)hipHostFree(w->mapped.host);
+  w->mapped.release();
   for (auto& e : w->ev) if (e) (void)hipEventDestroy(e);
   delete w;
   c->gmres_ws = nullptr;
 }
 }  // namespace rmbi
+
+using namespace rmbi;
 
 extern "C" {
 
@@ -214,46 +248,23 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
   if (n_bodies * n_b != c->n) return fail(RMB_ERR_STATE, "rmb_rigid_gmres_device: the resident configuration does not hold n_bodies x n_b blobs");
   if (!A11_dev || !A12_dev || !A21_dev || !A22_dev || !K_dev || !b_dev || !x_dev || !iterations || !residual)
     return fail(RMB_ERR_ARG, "null pointer");
-  if (restart < 1 || restart > 255 || maxiter < 0 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_rigid_gmres_device: need 1 <= restart <= 255, maxiter >= 0, tol >= 0");
+  if (restart < 1 || restart > kCoefMax - 1 || maxiter < 0 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_rigid_gmres_device: need 1 <= restart <= 255, maxiter >= 0, tol >= 0");
   RMB_HIP(hipSetDevice(c->device));
   const long nn = 3 * n_b, n3 = 3 * c->n, n = n3 + 6 * n_bodies, ldv = n;
   const long m_max = restart;
-  // ---- workspace ----
-  if (!c->gmres_ws) c->gmres_ws = new rmb_gmres_ws();
-  rmb_gmres_ws* ws = (rmb_gmres_ws*)c->gmres_ws;
-  const size_t col_row = (size_t)(m_max + 2);
-  const size_t dev_doubles = (size_t)(m_max + 1) * n + (size_t)5 * n + (size_t)m_max * col_row;
-  if (int rc = ws->dev.reserve(dev_doubles * sizeof(double))) return rc;
-  const size_t map_doubles = (size_t)m_max * col_row + 256 + 8;
-  if (map_doubles * sizeof(double) > ws->mapped.cap) {
-    if (ws->mapped.host) { RMB_HIP(hipStreamSynchronize(c->stream)); (void)hipHostFree(ws->mapped.host); ws->mapped = Mapped(); }
-    RMB_HIP(hipHostMalloc(&ws->mapped.host, map_doubles * sizeof(double), hipHostMallocMapped));
-    RMB_HIP(hipHostGetDevicePointer(&ws->mapped.dev, ws->mapped.host, 0));
-    ws->mapped.cap = map_doubles * sizeof(double);
-  }
-  for (auto& e : ws->ev) if (!e) RMB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  double* V = (double*)ws->dev.p;
-  double* z = V + (size_t)(m_max + 1) * n;
-  double* w = z + n;
-  double* y = w + n;
-  double* r = y + n;
-  double* bs = r + n;                                          // the right-hand side scaled to unit norm (rhs_norm != NULL)
-  double* cols = bs + n;                                       // [m_max][m_max + 2] on the device
-  double* hcols = (double*)ws->mapped.host;                    // the same rows in mapped host memory
-  double* hcols_dev = (double*)ws->mapped.dev;
-  double* hcoef = hcols + (size_t)m_max * col_row;             // back-substitution coefficients (host writes, kernel reads)
-  double* hcoef_dev = hcols_dev + (size_t)m_max * col_row;
-  double* hscal = hcoef + 256;                                 // one scalar (a norm)
-  double* hscal_dev = hcoef_dev + 256;
+  KrylovWs ws;
+  if (int rc = krylov_workspace(c, m_max, n, 5, &ws)) return rc;
+  double *const V = ws.V, *const z = ws.work(0), *const w = ws.work(1), *const y = ws.work(2), *const r = ws.work(3);
+  double* const bs = ws.work(4);                               // the right-hand side scaled to unit norm (rhs_norm != NULL)
   hipStream_t s = c->stream;
   const rmb_block b11{A11_dev, nn * nn, nn, 1}, b12{A12_dev, nn * 6, 6, 1}, b21{A21_dev, 6 * nn, nn, 1}, b22{A22_dev, 36, 6, 1};
   long n_products = 0;
 
   auto host_norm = [&](const double* v, double* out) -> int {
-    hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, v, n, hscal_dev);
+    hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, v, n, ws.hscal_dev);
     RMB_HIP(hipGetLastError());
     RMB_HIP(hipStreamSynchronize(s));
-    *out = *hscal;
+    *out = *ws.hscal;
     return 0;
   };
   auto precondition = [&](const double* in, double* out) -> int {       // out = P^-1 in
@@ -301,8 +312,8 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
 
     // Host side of iteration j: wait for its column, rotate, test.  true = stop after this column.
     auto finish = [&](long j, bool* out_stop) -> int {
-      RMB_HIP(hipEventSynchronize(ws->ev[j & 1]));
-      memcpy(col.data(), hcols + (size_t)j * col_row, (size_t)(j + 2) * sizeof(double));
+      RMB_HIP(hipEventSynchronize(ws.ev[j & 1]));
+      memcpy(col.data(), ws.hcols + (size_t)j * ws.col_row, (size_t)(j + 2) * sizeof(double));
       const double w_norm = col[j + 1];
       for (long i = 0; i < j; ++i) {
         const double t = cs[i] * col[i] + sn[i] * col[i + 1];
@@ -341,10 +352,10 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
       }
       // (from the second step of a cycle on, z = P^-1 v_j was left behind by the previous step's last launch: six launches)
       if (int rc = arnoldi_step_impl(c, n_bodies, n_b, A11_dev, A12_dev, A21_dev, A22_dev, K_dev, V, ldv, j, eta, z, w,
-                                     cols + (size_t)j * col_row, hcols_dev + (size_t)j * col_row, fuse_pc && j > 0, fuse_pc))
+                                     ws.cols + (size_t)j * ws.col_row, ws.hcols_dev + (size_t)j * ws.col_row, fuse_pc && j > 0, fuse_pc))
         return rc;
       ++n_products;
-      RMB_HIP(hipEventRecord(ws->ev[j & 1], s));
+      RMB_HIP(hipEventRecord(ws.ev[j & 1], s));
       if (pending >= 0) {
         if (int rc = finish(pending, &stop)) return rc;
         pending = -1;
@@ -359,10 +370,10 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
     if (k_used > 0) {
       for (long i = k_used - 1; i >= 0; --i) {
         double t = g[i];
-        for (long q = i + 1; q < k_used; ++q) t -= H[(size_t)i * m_max + q] * hcoef[q];
-        hcoef[i] = t / H[(size_t)i * m_max + i];
+        for (long q = i + 1; q < k_used; ++q) t -= H[(size_t)i * m_max + q] * ws.hcoef[q];
+        ws.hcoef[i] = t / H[(size_t)i * m_max + i];
       }
-      hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(n)), dim3(kVecT), 0, s, y, V, ldv, hcoef_dev, (int)k_used, n);
+      hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(n)), dim3(kVecT), 0, s, y, V, ldv, ws.hcoef_dev, (int)k_used, n);
       RMB_HIP(hipGetLastError());
       // (no wait here: the host writes hcoef again only after it has waited for an event of a LATER step of this stream --
       //  of the next cycle, or of the next call on this context -- and by then this kernel has run)
@@ -410,46 +421,14 @@ int rmb_lanczos_noise_coefficients(long k, const double* h_diag, const double* h
 
 namespace rmbi {
 namespace {
-struct LanczosBuffers {
-  double* V; long ldv;               // basis, (cap + 1) rows
-  double *x0, *x1, *x2;              // three work vectors of the step
-  double* cols; double* hcols_dev;   // coefficient rows: device copy and the mapped one
-  size_t col_row;
-};
-
-// step(i, buffers): enqueue iteration i (its coefficients go to cols + i * col_row and hcols_dev + i * col_row);
-// finish(combo, buffers): combo = V[:k]^T coef is enqueued in buffers.x1; write the result
+// step(i, ws): enqueue iteration i (its coefficients go to ws.cols + i * ws.col_row and ws.hcols_dev + i * ws.col_row; three
+// work vectors are its own); finish(combo): combo = V[:k]^T coef is enqueued in work vector 1; write the result
 template <class Step, class Finish>
-int lanczos_loop(rmb_ctx* c, const char* who, long dim, const double* z_dev, double factor, double tol, long max_iter, long cap, Step step,
+int lanczos_loop(rmb_ctx* c, long dim, const double* z_dev, double factor, double tol, long max_iter, long cap, Step step,
                  Finish finish_result, long* iterations, long* products, int* status) {
-  if (!c->gmres_ws) c->gmres_ws = new rmb_gmres_ws();
-  rmb_gmres_ws* ws = (rmb_gmres_ws*)c->gmres_ws;
-  const size_t col_row = (size_t)(cap + 2);
-  const size_t dev_doubles = (size_t)(cap + 1) * dim + (size_t)3 * dim + (size_t)cap * col_row;
-  if (int rc = ws->dev.reserve(dev_doubles * sizeof(double))) return rc;
-  const size_t map_doubles = (size_t)cap * col_row + 256 + 8;
-  if (map_doubles * sizeof(double) > ws->mapped.cap) {
-    if (ws->mapped.host) { RMB_HIP(hipStreamSynchronize(c->stream)); (void)hipHostFree(ws->mapped.host); ws->mapped = Mapped(); }
-    RMB_HIP(hipHostMalloc(&ws->mapped.host, map_doubles * sizeof(double), hipHostMallocMapped));
-    RMB_HIP(hipHostGetDevicePointer(&ws->mapped.dev, ws->mapped.host, 0));
-    ws->mapped.cap = map_doubles * sizeof(double);
-  }
-  for (auto& e : ws->ev) if (!e) RMB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  LanczosBuffers b;
-  b.V = (double*)ws->dev.p; b.ldv = dim;
-  b.x0 = b.V + (size_t)(cap + 1) * dim;
-  b.x1 = b.x0 + dim;
-  b.x2 = b.x1 + dim;
-  b.cols = b.x2 + dim;
-  b.col_row = col_row;
-  double* hcols = (double*)ws->mapped.host;
-  b.hcols_dev = (double*)ws->mapped.dev;
-  double* hcoef = hcols + (size_t)cap * col_row;
-  double* hcoef_dev = b.hcols_dev + (size_t)cap * col_row;
-  double* hscal = hcoef + 256;
-  double* hscal_dev = hcoef_dev + 256;
+  KrylovWs b;
+  if (int rc = krylov_workspace(c, cap, dim, 3, &b)) return rc;
   hipStream_t s = c->stream;
-  (void)who;
   *status = 0;
   *iterations = 0;
   long n_products = 0;
@@ -460,10 +439,10 @@ int lanczos_loop(rmb_ctx* c, const char* who, long dim, const double* z_dev, dou
     return 0;
   };
 
-  hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, z_dev, dim, hscal_dev);
+  hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, z_dev, dim, b.hscal_dev);
   RMB_HIP(hipGetLastError());
   RMB_HIP(hipStreamSynchronize(s));
-  const double v_norm = *hscal;
+  const double v_norm = *b.hscal;
   if (!(v_norm > 0.0) || !std::isfinite(v_norm)) return give_up(1);
   hipLaunchKernelGGL(vec_div_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.V, z_dev, v_norm, dim);
   RMB_HIP(hipGetLastError());
@@ -473,14 +452,14 @@ int lanczos_loop(rmb_ctx* c, const char* who, long dim, const double* z_dev, dou
   auto enqueue = [&](long i) -> int {
     if (int rc = step(i, b)) return rc;
     ++n_products;
-    RMB_HIP(hipEventRecord(ws->ev[i & 1], s));
+    RMB_HIP(hipEventRecord(b.ev[i & 1], s));
     return 0;
   };
   // host side of iteration i: 1 = stop (converged), 0 = go on, -1 = breakdown
   long its = -1;
   auto finish = [&](long i, int* verdict) -> int {
-    RMB_HIP(hipEventSynchronize(ws->ev[i & 1]));
-    const double hd = hcols[(size_t)i * col_row + i], hs = hcols[(size_t)i * col_row + i + 1];
+    RMB_HIP(hipEventSynchronize(b.ev[i & 1]));
+    const double hd = b.hcols[(size_t)i * b.col_row + i], hs = b.hcols[(size_t)i * b.col_row + i + 1];
     if (!(hs > 0.0) || !std::isfinite(hs)) { *verdict = -1; return 0; }
     h_diag.push_back(hd);
     h_sup.push_back(hs);
@@ -515,11 +494,11 @@ int lanczos_loop(rmb_ctx* c, const char* who, long dim, const double* z_dev, dou
   }
   // V[:k]^T coef
   const long k = (long)coef.size();
-  memcpy(hcoef, coef.data(), (size_t)k * sizeof(double));
-  hipLaunchKernelGGL(vec_zero_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.x1, dim);
-  hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.x1, b.V, b.ldv, hcoef_dev, (int)k, dim);
+  memcpy(b.hcoef, coef.data(), (size_t)k * sizeof(double));
+  hipLaunchKernelGGL(vec_zero_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.work(1), dim);
+  hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.work(1), b.V, dim, b.hcoef_dev, (int)k, dim);
   RMB_HIP(hipGetLastError());
-  if (int rc = finish_result(b.x1, b)) return rc;
+  if (int rc = finish_result(b.work(1))) return rc;
   // (no wait: whoever writes hcoef next -- a Lanczos entry or rmb_rigid_gmres_device -- has by then waited for an event recorded
   //  later on this stream; the result is enqueued, the scalars are final)
   *iterations = its;
@@ -541,21 +520,21 @@ int rmb_rigid_lanczos_device(rmb_ctx* c, long n_bodies, long n_b, const double* 
   if (n_bodies < 1 || n_b < 1) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_device: bad n_bodies / n_b");
   if (n_bodies * n_b != c->n) return fail(RMB_ERR_STATE, "rmb_rigid_lanczos_device: the resident configuration does not hold n_bodies x n_b blobs");
   if (!Linv_dev || !Lchol_dev || !z_dev || !noise_dev || !iterations || !status) return fail(RMB_ERR_ARG, "null pointer");
-  if (max_rows < 2 || max_rows > 254 || max_iter < 1 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_device: need 2 <= max_rows <= 254, max_iter >= 1, tol >= 0");
+  if (max_rows < 2 || max_rows > kCoefMax - 2 || max_iter < 1 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_rigid_lanczos_device: need 2 <= max_rows <= 254, max_iter >= 1, tol >= 0");
   RMB_HIP(hipSetDevice(c->device));
   const long nn = 3 * n_b, n3 = 3 * c->n;
   const bool fuse_next = c->opt_gmres_fuse_pc != 0 && nn <= 96;      // (as in rmb_rigid_gmres_device)
-  auto step = [&](long i, const LanczosBuffers& b) -> int {
-    // x0: P v_i (from the second step on left there by the previous step's normalisation launch), x1: the sweep's raw sums,
-    // x2: P^T M P v_i, orthogonalised in place -- five launches per iteration
-    return lanczos_step_impl(c, n_bodies, n_b, Linv_dev, b.V, b.ldv, i, eta, b.x0, b.x1, b.x2, b.cols + (size_t)i * b.col_row,
+  auto step = [&](long i, const KrylovWs& b) -> int {
+    // work 0: P v_i (from the second step on left there by the previous step's normalisation launch), 1: the sweep's raw sums,
+    // 2: P^T M P v_i, orthogonalised in place -- five launches per iteration
+    return lanczos_step_impl(c, n_bodies, n_b, Linv_dev, b.V, b.dim, i, eta, b.work(0), b.work(1), b.work(2), b.cols + (size_t)i * b.col_row,
                              b.hcols_dev + (size_t)i * b.col_row, fuse_next && i > 0, fuse_next);
   };
-  auto result = [&](double* combo, const LanczosBuffers&) -> int {       // noise = blockdiag(L_b) V[:k]^T coef
+  auto result = [&](double* combo) -> int {       // noise = blockdiag(L_b) V[:k]^T coef
     const rmb_block l{Lchol_dev, nn * nn, nn, 1};
     return rmb_block_apply_device(c, n_bodies, nn, nn, 0, 0, &l, nullptr, nullptr, nullptr, combo, nullptr, 1.0, 0.0, noise_dev, 0.0, nullptr);
   };
-  return lanczos_loop(c, "rmb_rigid_lanczos_device", n3, z_dev, factor, tol, max_iter, max_rows, step, result, iterations, products, status);
+  return lanczos_loop(c, n3, z_dev, factor, tol, max_iter, max_rows, step, result, iterations, products, status);
 }
 
 // The plain forcing of the single-blob schemes:  noise = factor * M^{1/2} z  with M = M_tt (product 0; in_plane: its in-plane
@@ -568,31 +547,32 @@ int rmb_lanczos_device(rmb_ctx* c, int product, int in_plane, const double* z_de
   if (product == 1 && in_plane) return fail(RMB_ERR_ARG, "rmb_lanczos_device: the grand mobility has no in-plane variant");
   if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "rmb_lanczos_device: needs the full target range");
   if (!z_dev || !noise_dev || !iterations || !status) return fail(RMB_ERR_ARG, "null pointer");
-  if (max_rows < 2 || max_rows > 254 || max_iter < 1 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_lanczos_device: need 2 <= max_rows <= 254, max_iter >= 1, tol >= 0");
+  if (max_rows < 2 || max_rows > kCoefMax - 2 || max_iter < 1 || !(tol >= 0.0)) return fail(RMB_ERR_ARG, "rmb_lanczos_device: need 2 <= max_rows <= 254, max_iter >= 1, tol >= 0");
   if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   RMB_HIP(hipSetDevice(c->device));
   const long n3 = 3 * c->n, dim = product == 1 ? 2 * n3 : n3;
-  auto step = [&](long i, const LanczosBuffers& b) -> int {
-    const double* v = b.V + i * b.ldv;
+  auto step = [&](long i, const KrylovWs& b) -> int {
+    const double* v = b.V + i * dim;
+    double* const x1 = b.work(1);
     long tiles = 0;
     if (product == 0 && !in_plane) {
       // (small decks: the finishing launch also takes the first Gram-Schmidt pass's dots, five launches per iteration)
-      if (int rc = plain_tt_with_dots(c, v, eta, b.x1, b.V, b.ldv, i + 1, &tiles)) return rc;
+      if (int rc = plain_tt_with_dots(c, v, eta, x1, b.V, dim, i + 1, &tiles)) return rc;
     } else if (product == 0) {
-      if (int rc = matvec_device_impl(c, rmb::KIND_TT, 1, v, nullptr, eta, b.x1)) return rc;
+      if (int rc = matvec_device_impl(c, rmb::KIND_TT, 1, v, nullptr, eta, x1)) return rc;
     } else {
       const double* in[2] = {v, v + n3};
-      double* out[2] = {b.x1, b.x1 + n3};
+      double* out[2] = {x1, x1 + n3};
       if (int rc = rmb_matvec_op_device(c, RMB_OP_GRAND, 0, 2, in, 2, out, eta)) return rc;
     }
-    return krylov_orthogonalize_impl(c, dim, i + 1, b.V, b.ldv, b.x1, b.cols + (size_t)i * b.col_row, b.V + (i + 1) * b.ldv,
+    return krylov_orthogonalize_impl(c, dim, i + 1, b.V, dim, x1, b.cols + (size_t)i * b.col_row, b.V + (i + 1) * dim,
                                      b.hcols_dev + (size_t)i * b.col_row, nullptr, tiles, true);
   };
-  auto result = [&](double* combo, const LanczosBuffers&) -> int {
+  auto result = [&](double* combo) -> int {
     RMB_HIP(hipMemcpyAsync(noise_dev, combo, (size_t)dim * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return 0;
   };
-  return lanczos_loop(c, "rmb_lanczos_device", dim, z_dev, factor, tol, max_iter, max_rows, step, result, iterations, products, status);
+  return lanczos_loop(c, dim, z_dev, factor, tol, max_iter, max_rows, step, result, iterations, products, status);
 }
 
 }  // extern "C"

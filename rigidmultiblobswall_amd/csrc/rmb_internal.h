@@ -1,7 +1,8 @@
 // rmb_internal.h -- what the translation units of librmb_mobility.so share (never installed; the boundary is
 // include/rmb_mobility.h).
 //
-//   rmb_context.hip  error state, context life cycle, streams, options, timing ring, diagnostics, default context
+//   rmb_context.hip  error state, context life cycle, streams, the option table (kOptions: every key, its member of rmb_ctx
+//                    and how a set value is normalised), DevBuf / MappedBuf, timing ring, diagnostics, default context
 //   rmb_plan.hip     launch plans: source chunks, residency, the balanced step schedule of the symmetric kernels,
 //                    pair-shard ranges, kernel-uniform constants
 //   rmb_sym.hip      the symmetric (each unordered pair once) fp64 sweeps: one launch path (fill_sym_args, choose_sym,
@@ -12,11 +13,13 @@
 //   rmb_sort.hip     Morton ordering of the blobs for the force kernel's tile culling (rocPRIM radix sort)
 //   rmb_sweep.hip    the one-sided kernels (one frame, onesided_kernels.h; one launcher, one_sided_launch below): sweep,
 //                    force sweep, source->target, pressure / double layer; dense body blocks, position packing
-//   rmb_entry.hip    the extern "C" products: argument checks, routing between the two families, host staging
+//   rmb_entry.hip    the extern "C" products: argument checks, routing between the two families, host staging (aux_stage /
+//                    download; rmb_matvec's mapped hand-off)
 //   rmb_multi.hip    the single-process multi-device engine (rmb_multi_*)
 //   rmb_rigid.hip    per-body geometry (positions, K) and the per-body factors of the block-diagonal preconditioner
 //   rmb_krylov.hip   O(N) helpers of the rigid-body solve: batched 2 x 2 block product, fused Gram-Schmidt step
-//   rmb_gmres.hip    the whole right-preconditioned GMRES of the rigid-body problem as one call (host loop native too)
+//   rmb_gmres.hip    the whole right-preconditioned GMRES of the rigid-body problem and the Lanczos forcings as one call each
+//                    (host loop native too); one workspace layout for both (krylov_workspace)
 //   rmb_potential.hip  total potential energy of a blob configuration (potential_kernels.h: symmetric sweep to a scalar,
 //                    atomic-free) and the Metropolis proposal of the equilibrium sampler
 //   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
@@ -53,11 +56,53 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// Page-locked host memory mapped into the device's address space (the ONE place that allocates it): the host reads / writes
+// `host`, kernels use `dev`.  reserve() allocates exactly `bytes` when bytes > cap (the caller passes the size it wants, slack
+// included) and frees what was there, contents and all.  Nothing queued may still touch the old memory: `drain` is the stream
+// to wait for before the free; without one the caller says at the call why the stream is already idle.
+struct MappedBuf {
+  void* host = nullptr;
+  void* dev = nullptr;
+  size_t cap = 0;
+  int reserve(size_t bytes, const hipStream_t* drain = nullptr);
+  void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; cap = 0; }
+};
+
 constexpr int kTimingRing = 8192;
+
+// Device memory a context owns: DevBufs only, each listed in kCtxBufs (the static_assert counts them).  rmb_ctx_destroy and the
+// "buffers_signature" hash that validates captured graphs walk that one list (for_each_buffer), so a buffer added here can
+// neither leak nor go missing from the hash.  A DevBuf of the context belongs HERE, not among the other members of rmb_ctx.
+// (The native Krylov loops' workspace behind gmres_ws is not part of it: graphs do not capture those calls.)
+struct CtxBuffers {
+  DevBuf pos;      // double4[n]
+  DevBuf r_stage;  // raw positions staging (host entry)
+  DevBuf vec, vec2, out, partial, tmp3n;
+  DevBuf tile_bounds;      // bounding boxes of the 64-blob tiles (force kernel's tile culling); valid for the packed positions
+  // spatially sorted copy of the configuration for the force kernel (rmb_sort.hip): valid together with tile_bounds
+  DevBuf fpos, fperm, fsort_keys, fsort_vals, fsort_tmp, fsort_box;
+  DevBuf pot_ws;           // potential energy (rmb_potential.hip): per-wave partial sums + the two results
+  DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
+  DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
+  DevBuf krylov;   // partial sums of rmb_krylov_orthogonalize_device
+  DevBuf symbuf;   // acc[3][n_pad] doubles for the symmetric tt kernel (kept zero between calls)
+  DevBuf st[8];    // scratch of the source->target entry point
+};
+using CB = CtxBuffers;
+constexpr DevBuf CB::* kCtxBufs[] = {&CB::pos, &CB::r_stage, &CB::vec, &CB::vec2, &CB::out, &CB::partial, &CB::tmp3n, &CB::tile_bounds,
+                                     &CB::fpos, &CB::fperm, &CB::fsort_keys, &CB::fsort_vals, &CB::fsort_tmp, &CB::fsort_box,
+                                     &CB::pot_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
+static_assert(sizeof(CtxBuffers) == (sizeof(kCtxBufs) / sizeof(kCtxBufs[0]) + 8) * sizeof(DevBuf),
+              "a DevBuf of CtxBuffers is missing from kCtxBufs (or st[] changed its length)");
+template <class Bufs, class F>      // Bufs: CtxBuffers or const CtxBuffers (an rmb_ctx converts)
+void for_each_buffer(Bufs& b, F f) {
+  for (auto m : kCtxBufs) f(b.*m);
+  for (auto& s : b.st) f(s);
+}
 
 }  // namespace rmbi
 
-struct rmb_ctx {
+struct rmb_ctx : rmbi::CtxBuffers {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t stream_switch = nullptr;  // orders a newly set stream after the work queued on the previous one
@@ -71,81 +116,63 @@ struct rmb_ctx {
   int wall = 0;
   int free_surface = 0;          // the configuration was loaded with wall != 0 under option "free_surface": raw heights (wall = 0 above),
                                  // kind tt is the free-surface product
-  long opt_free_surface = 0;     // rmb_set_positions*(wall != 0) means a stress-free surface at z = 0, not a no-slip wall
-  long opt_free_surface_rotation = 0;   // a free-surface configuration also serves tr / rt / rr / tt_tr and the multi-block operations
-                                        // (mirror-image blocks beyond the reference; 0: refused, as the reference has none)
   bool have_positions = false;
   long tgt_begin = 0, tgt_end = 0;
-  // device memory
-  rmbi::DevBuf pos;      // double4[n]
-  rmbi::DevBuf r_stage;  // raw positions staging (host entry)
-  rmbi::DevBuf vec, vec2, out, partial, tmp3n;
-  rmbi::DevBuf tile_bounds;      // bounding boxes of the 64-blob tiles (force kernel's tile culling); valid for the packed positions
+  // state of the device memory in CtxBuffers
   bool tile_bounds_valid = false;
-  long opt_force_cull = 1;       // blob-blob forces: skip tile pairs beyond the range of the exponential (bit-exact)
-  // spatially sorted copy of the configuration for the force kernel (rmb_sort.hip): valid together with tile_bounds
-  rmbi::DevBuf fpos, fperm, fsort_keys, fsort_vals, fsort_tmp, fsort_box;
   bool force_sorted = false;     // tile_bounds / fpos / fperm describe the SORTED configuration
-  long opt_force_sort = 1;       // sort the blobs along a Morton curve for the force kernel's tile culling
   long fperm_n = -1;             // number of blobs fperm is a permutation of (force_sort_positions), -1 = none
-  // potential energy (rmb_potential.hip): per-wave partial sums + the two results; the Morton permutation is kept between
-  // evaluations and rebuilt every opt_potential_resort-th one (a Metropolis proposal moves a blob by a tenth of its radius)
-  rmbi::DevBuf pot_ws;
-  long opt_potential_resort = 16;   // measured: -25 % per evaluation at 1e4 blobs, -5 % at 1e5, -3 % at 262 144; 64 adds nothing
+  // (potential energy: the Morton permutation is kept and rebuilt every opt_potential_resort-th evaluation -- a Metropolis proposal moves a blob by a tenth of its radius)
   long pot_sort_age = -1;        // evaluations since the permutation was built, -1 = build it now
-  rmbi::DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
-  long opt_det_workspace_mb = 8192;   // cap on the partial-result workspace of deterministic = 2 (symx_det_device)
-  rmbi::DevBuf st[8];    // scratch of the source->target entry point
-  rmbi::DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
   long wave_clock_n = 0;
-  long opt_wave_clock = 0;
-  long opt_skip_pairs = 0;
-  rmbi::DevBuf krylov;   // partial sums of rmb_krylov_orthogonalize_device
-  void* gmres_ws = nullptr;   // workspace of rmb_rigid_gmres_device (rmb_gmres.hip), freed by gmres_release
-  rmbi::DevBuf symbuf;   // acc[3][n_pad] doubles for the symmetric tt kernel (kept zero between calls)
-  // result hand-off of the synchronous host entry point (rmb_matvec): page-locked, device-mapped host memory the finalize
-  // kernel stores into directly (coalesced), for results up to opt_host_zero_copy bytes
-  void* host_out = nullptr;
-  double* host_out_dev = nullptr;
-  size_t host_out_cap = 0;
-  void* host_in = nullptr;       // ... and the same for its input vectors (two of them: RMB_TT_TR)
-  double* host_in_dev = nullptr;
-  size_t host_in_cap = 0;
-  long opt_lanczos_fuse_finish = 1; // rmb_rigid_lanczos_device, every step: finalize of the sweep + L_b^-1 product in one launch
-  long opt_krylov_low_sync = 1;     // native GMRES / Lanczos steps: second update + norm (by Pythagoras) + normalisation in one launch
-  long opt_gmres_fuse_dots = 1;     // rmb_rigid_gmres_device: the operator's finishing launch also takes the first Gram-Schmidt dots (<= 256 bodies)
-  long opt_gmres_fuse_pc = 1;       // rmb_rigid_gmres_device: the normalisation launch also applies the preconditioner for the next step
-  long opt_host_zero_copy_in = 1;   // inputs of rmb_matvec through mapped memory + a pull kernel (sizes as host_zero_copy)
-  long opt_host_zero_copy = 768 << 10;   // bytes (32 768 blobs: level at 43 000, +1 % at 1e5); 0 = always a device-to-host copy command
   long symbuf_zeroed_for = -1;
-  // options
+  void* gmres_ws = nullptr;   // workspace of the native Krylov loops (rmb_gmres.hip), freed by gmres_release
+  // hand-off of the synchronous host entry point (rmb_matvec): memory the finalize kernel stores the result into directly
+  // (coalesced), for results up to opt_host_zero_copy bytes, and the same for its input vectors (two of them: RMB_TT_TR)
+  rmbi::MappedBuf host_out, host_in;
+  // options: one member per row of the option table (kOptions, rmb_context.hip), in its order; set / read by key only there
   long opt_chunks = 0;
   long opt_timing = 0;
   long opt_symmetric = 1;      // use the symmetric (each unordered pair once) kernel where applicable
   long opt_fused_symmetric = 1;  // tt+tr: 1 = single symmetric pass (symx_kernels.h), 2 = two symmetric passes, 0 = one-sided fused sweep
   long opt_symx_single = 0;      // route tt / tr / rt / rr through the generic skeleton (A/B against sym_kernel)
   long opt_deterministic = 0;  // force the atomic-free sweep kernel everywhere
-  int last_path = 0;           // 0 = sweep, 1 = symmetric (per wave), 2 = deterministic symmetric, 3 = symmetric, workgroup-cooperative,
-                               // 4 = symmetric, two target blobs per lane
+  long opt_det_workspace_mb = 8192;   // cap on the partial-result workspace of deterministic = 2 (symx_det_device)
   long opt_sym_wps = 0;        // cap on resident workgroups per CU for the symmetric kernel (0 = occupancy limit)
   long opt_sym_pin = 1;        // pad dynamic LDS so residency is exactly that number
+  long opt_free_surface = 0;     // rmb_set_positions*(wall != 0) means a stress-free surface at z = 0, not a no-slip wall
+  long opt_free_surface_rotation = 0;   // a free-surface configuration also serves tr / rt / rr / tt_tr and the multi-block operations
+                                        // (mirror-image blocks beyond the reference; 0: refused, as the reference has none)
   long opt_precision = 64;     // 32: M_tt f (open boundaries) in single precision (sym32_kernels.h); everything else fp64
   long opt_force_precision = 0;  // blob-blob forces: 0 = follow "precision", 32 / 64 = pinned
-  long opt_sym_min_steps = 64; // floor on rotation steps per wave (a unit is 64 steps)
+  long opt_force_cull = 1;       // blob-blob forces: skip tile pairs beyond the range of the exponential (bit-exact)
+  long opt_force_sort = 1;       // sort the blobs along a Morton curve for the force kernel's tile culling
+  long opt_potential_resort = 16;   // measured: -25 % per evaluation at 1e4 blobs, -5 % at 1e5, -3 % at 262 144; 64 adds nothing
   long opt_sym_fine_steps = 0;   // floor on steps per wave when less than one resident round is left (pair shards, small N); 0 = 16 or 32, chosen in plan_sym
   long opt_sym_coop = 1;       // workgroup-cooperative symmetric kernel (sym_coop_kernels.h): 0 = never, 1 = launches of at most
                                // kCoopMaxRounds resident rounds (small suspensions, pair shards, up to ~1e4 blobs), 2 = always
   long opt_sym_chunk_steps = 1024;  // symmetric kernels: a wave's steps are cut into strided chunks of about this many (0 = one range)
   long opt_sym_two_targets = 1;   // sym2t_kernel (two target blobs per lane) for tt / tr / rt / rr, open boundaries: 0 off, 1 from one resident round on, 2 always
+  long opt_host_zero_copy_in = 1;   // inputs of rmb_matvec through mapped memory + a pull kernel (sizes as host_zero_copy)
+  long opt_gmres_fuse_pc = 1;       // rmb_rigid_gmres_device: the normalisation launch also applies the preconditioner for the next step
+  long opt_gmres_fuse_dots = 1;     // rmb_rigid_gmres_device: the operator's finishing launch also takes the first Gram-Schmidt dots (<= 256 bodies)
+  long opt_krylov_low_sync = 1;     // native GMRES / Lanczos steps: second update + norm (by Pythagoras) + normalisation in one launch
+  long opt_lanczos_fuse_finish = 1; // rmb_rigid_lanczos_device, every step: finalize of the sweep + L_b^-1 product in one launch
+  long opt_host_zero_copy = 768 << 10;   // bytes (32 768 blobs: level at 43 000, +1 % at 1e5); 0 = always a device-to-host copy command
   long opt_sym_order = 1;      // unit order of the symmetric kernels: 1 = blocked (32 x 32 tile super-blocks), 0 = row-major
   long opt_sym_xcd = 1;        // XCD-aware workgroup numbering (each XCD a contiguous eighth of the step range)
   long opt_sym_oversub = 8;    // launch this many times the resident workgroup count (measured: -4..8 % kernel time;
                                // waves of one SIMD finish oldest-first, more rounds keep every SIMD at >= 3 active waves)
+  long opt_sym_min_steps = 64; // floor on rotation steps per wave (a unit is 64 steps)
+  long opt_wave_clock = 0;     // diagnostics build only, as the next
+  long opt_skip_pairs = 0;
   // timing ring (events around the sweep kernel)
   std::vector<hipEvent_t> ev0, ev1;
   int ev_count = 0;  // events recorded since last reset (capped at ring size)
   long timing_launches = 0;  // sweeps seen since the last reset (sampling stride of the "timing" option)
   // last launch
+  int last_path = 0;           // 0 = sweep, 1 = symmetric (per wave), 2 = deterministic symmetric, 3 = symmetric, workgroup-cooperative,
+                               // 4 = symmetric, two target blobs per lane
   long last_tiles = 0, last_chunks = 0, last_wgs = 0;
   double host_us[4] = {0, 0, 0, 0};   // last rmb_matvec: upload, launch, wait + download, whole call (host wall clock, us)
 };

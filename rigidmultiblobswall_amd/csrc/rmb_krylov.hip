@@ -453,13 +453,10 @@ extern "C" {
 // the same internally).  *host_out = the address the host reads, *dev_out = the address kernels use.
 int rmb_host_mapped_alloc(size_t bytes, void** host_out, void** dev_out) {
   if (!host_out || !dev_out || bytes == 0) return fail(RMB_ERR_ARG, "rmb_host_mapped_alloc: null pointer / zero size");
-  void* h = nullptr;
-  RMB_HIP(hipHostMalloc(&h, bytes, hipHostMallocMapped));
-  void* d = nullptr;
-  const hipError_t e = hipHostGetDevicePointer(&d, h, 0);
-  if (e != hipSuccess) { (void)hipHostFree(h); return fail(RMB_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e)); }
-  memset(h, 0, bytes);
-  *host_out = h; *dev_out = d;
+  MappedBuf m;      // handed to the caller, who frees it with rmb_host_mapped_free(host)
+  if (int rc = m.reserve(bytes)) return rc;
+  memset(m.host, 0, bytes);
+  *host_out = m.host; *dev_out = m.dev;
   return 0;
 }
 
