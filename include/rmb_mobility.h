@@ -401,6 +401,17 @@ int rmb_blob_blob_force(rmb_ctx* ctx, double repulsion_strength, double debye_le
                         double* out_host);
 int rmb_blob_blob_force_device(rmb_ctx* ctx, double repulsion_strength, double debye_length,
                                double blob_radius, double* out_dev);
+/* Body-body forces (multi_bodies/multi_bodies_functions.py:359-408, `body_body_force_torque_implementation python`): a
+ * Yukawa repulsion U = eps exp(-r/b) / r between the resident points, which the caller sets to the body LOCATIONS
+ * (rmb_set_positions with wall = 0; wall = 1 or a target sub-range: RMB_ERR_STATE).  out (n,3):
+ *   F_i = sum_j -(eps/b + eps/r) exp(-r/b) (x_j - x_i) / r^2,  r = |x_j - x_i| in the minimal image of every direction
+ * with a positive period (all three, as project_to_periodic_image).  The torque of the reference's law is zero and is not
+ * returned.  Each unordered pair once on the symmetric force sweep, always fp64 ("force_precision" / "precision" do not
+ * apply; atomic flushes whatever "deterministic" says); "force_cull" (tile pairs beyond 750 b: exact zeros) and
+ * "force_sort" apply.  Coincident points divide by zero as in the reference: those points get non-finite forces, the
+ * others are not affected.  debye_length <= 0 or a null pointer: RMB_ERR_ARG. */
+int rmb_body_body_force(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_host);
+int rmb_body_body_force_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

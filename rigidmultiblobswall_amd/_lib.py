@@ -72,6 +72,8 @@ SYMBOLS = {
                                                       ctypes.c_double, ctypes.c_long, ctypes.c_long]),
     "rmb_blob_blob_force": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_blob_blob_force_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_body_body_force": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_body_body_force_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_blob_potential": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_blob_potential_device": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_mcmc_propose_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -493,6 +493,29 @@ class MobilityContext(object):
                                                     float(blob_radius), ctypes.c_void_p(out.data_ptr())))
     return out
 
+  def body_body_force(self, repulsion_strength, debye_length):
+    """(n, 3) Yukawa forces between the resident points, which the caller has set to the body locations
+    (set_positions(..., wall=False)): F_i = sum_j -(eps/b + eps/r) exp(-r/b) (x_j - x_i)/r^2, minimal image in every
+    periodic direction (multi_bodies_functions.py:359-408; rmb_body_body_force).  The sweep is always fp64: the
+    "force_precision" / "precision" options do not apply."""
+    out = np.empty(3 * self.n)
+    _lib.check(self._lib.rmb_body_body_force(self._h, float(repulsion_strength), float(debye_length), _ptr(out)))
+    return out.reshape(self.n, 3)
+
+  def body_body_force_device(self, repulsion_strength, debye_length, out=None, device=None):
+    """The same as a CUDA float64 tensor of 3 n entries, asynchronous on the context's stream
+    (rmb_body_body_force_device); a caller's out= goes straight to the kernel.  Always fp64, whatever "force_precision"
+    says."""
+    import torch
+    if out is None:
+      out = torch.empty(3 * self.n, dtype=torch.float64, device=device or ("cuda:%d" % self.device))
+    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or out.numel() != 3 * self.n or not out.is_contiguous():
+      raise ValueError("out must be a contiguous CUDA float64 tensor with 3*n entries")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_body_body_force_device(self._h, float(repulsion_strength), float(debye_length),
+                                                    ctypes.c_void_p(out.data_ptr())))
+    return out
+
   def _potential_args(self, repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential):
     if potential not in POTENTIAL_FORMS:
       raise ValueError("potential must be one of %s, got %r" % (sorted(POTENTIAL_FORMS), potential))

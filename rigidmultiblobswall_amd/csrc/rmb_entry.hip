@@ -118,6 +118,19 @@ int force_device_impl(rmb_ctx* c, double eps, double b, double blob_radius, doub
   return force_sweep_device(c, eps, b, blob_radius, out, radii);
 }
 
+// Body-body forces: the Yukawa law between the resident points (body locations), always the symmetric fp64 sweep --
+// each unordered pair once whatever n and whatever "symmetric" / "deterministic" / "force_precision" say.
+int body_force_device_impl(rmb_ctx* c, double eps, double b, double* out) {
+  if (int rc = check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
+  if (c->wall) return fail(RMB_ERR_STATE, "the body-body force uses raw locations: call rmb_set_positions with wall = 0");
+  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the body-body force acts on all resident points: reset the target range");
+  if (c->n == 0) return 0;
+  RMB_HIP(hipSetDevice(c->device));
+  return sym_force_device(c, eps, b, 0.0, out, nullptr, 0, 1, FORCE_LAW_BODY);
+}
+
 // Multi-block operations (include/rmb_mobility.h, enum rmb_op).  One symmetric pass when that path applies (or for a
 // pair shard); otherwise composed from the one-sided sweeps (target sub-ranges, "deterministic", n < 128).
 // One pair shard of a single-vector product.  `in_plane` (the reference's in_plane_* wrappers: z row / column masked) is
@@ -481,6 +494,19 @@ int rmb_blob_blob_force(rmb_ctx* c, double eps, double b, double blob_radius, do
   const size_t ob = (size_t)3 * n_tgt * sizeof(double);
   if (int rc = c->out.reserve(ob)) return rc;
   if (int rc = force_device_impl(c, eps, b, blob_radius, (double*)c->out.p)) return rc;
+  return download(c, out, c->out.p, ob);
+}
+
+int rmb_body_body_force_device(rmb_ctx* c, double eps, double b, double* out) { return body_force_device_impl(c, eps, b, out); }
+
+int rmb_body_body_force(rmb_ctx* c, double eps, double b, double* out) {
+  if (int rc = check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  if (c->n == 0) return 0;
+  RMB_HIP(hipSetDevice(c->device));
+  const size_t ob = (size_t)3 * c->n * sizeof(double);
+  if (int rc = c->out.reserve(ob)) return rc;
+  if (int rc = body_force_device_impl(c, eps, b, (double*)c->out.p)) return rc;
   return download(c, out, c->out.p, ob);
 }
 

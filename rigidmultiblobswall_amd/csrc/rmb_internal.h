@@ -384,8 +384,9 @@ int symx_device(rmb_ctx* c, int op, const double* const* in, double* const* out,
 int tt_raw_sums_device(rmb_ctx* c, const double* v, double eta, double* out);
 int symx_det_device(rmb_ctx* c, int op, const double* const* in, double* const* out, double eta, int in_plane,
                     long shard = 0, long nshards = 1);
+enum ForceLaw { FORCE_LAW_BLOB = 0, FORCE_LAW_BODY = 1 };   // the pair law of sym_force_kernel (sym_force_kernels.h)
 int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, double* out, const double* radii, long shard,
-                     long nshards);
+                     long nshards, ForceLaw law = FORCE_LAW_BLOB);
 
 // ---- rmb_sort.hip ------------------------------------------------------------------------------------------
 int force_sort_positions(rmb_ctx* c);

@@ -322,10 +322,14 @@ int build_tile_bounds(rmb_ctx* c, bool sorted, bool keep_perm) {
   return 0;
 }
 
-// Symmetric blob-blob force sweep (sym_force_kernels.h: each unordered pair once, F_ji = -F_ij) of pair shard `shard` of
+// Symmetric pair-force sweep (sym_force_kernels.h: each unordered pair once, F_ji = -F_ij) of pair shard `shard` of
 // `nshards` into a full-length result; atomic flushes.  Tile culling and the fp32 twin as the options say.
+// `law`: the blob-blob contact law, or the body-body Yukawa law on the resident points (FORCE_LAW_BODY: fp64 only, no
+// contact distance -- blob_radius and radii are not read).
 int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, double* out, const double* radii, long shard,
-                     long nshards) {
+                     long nshards, ForceLaw law) {
+  const bool body = law == FORCE_LAW_BODY;
+  if (body) { blob_radius = 0.0; radii = nullptr; }
   const SymConf cf = conf_of(c);
   const bool periodic = is_periodic(cf);
   const long n = c->n, tiles = (n + 63) / 64;
@@ -338,16 +342,17 @@ int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, doubl
   // waves equally heavy runs of super-block rows; measured 3.37 vs 5.01 ms on a 3D cloud of 1e5 blobs, 2.39 vs 2.64 ms on
   // the 262 144-roller monolayer (tools/experiments/exp_force_ab.py).  The strided chunks stay.
   a.order = 0; a.xcd = 0;
-  a.eps_over_b = eps / b; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
+  a.eps = eps; a.eps_over_b = eps / b; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
   a.ec = exp_consts();
   a.radii = radii;
   // "precision" = 32, open boundaries: the single-precision kernel -- the arithmetic of the reference's own GPU force
   // kernel (forces_pycuda.py:14-21)
-  const bool f32 = (c->opt_force_precision ? c->opt_force_precision : c->opt_precision) == 32 && !periodic;
+  const bool f32 = !body && (c->opt_force_precision ? c->opt_force_precision : c->opt_precision) == 32 && !periodic;
   // Tile culling: the force has the range of its exponential.  exp(-(r - 2a)/b) is exactly 0 in double precision
   // beyond (r - 2a)/b = 745.2 (750 here; 110 for the float kernel), so a tile pair whose bounding boxes are further
   // apart contributes nothing, bit for bit.  In a 262 144-roller monolayer that is 99 % of the tile pairs -- the
-  // reference's own answer to this is a k-d tree (`blob_blob_force_implementation tree_numba`).
+  // reference's own answer to this is a k-d tree (`blob_blob_force_implementation tree_numba`).  The Yukawa law between
+  // body locations has the same range with 2a = 0: exp(-r/b) is exactly 0 beyond r = 750 b.
   a.bounds = nullptr; a.cull2 = 0.0; a.perm = nullptr;
   if (c->opt_force_cull && !radii && tiles > 1) {
     // Spatial order first ("force_sort"): how much the culling skips depends on how compact a 64-blob tile is, i.e. on
@@ -364,7 +369,9 @@ int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, doubl
     a.cull2 = reach * reach;
   }
   typedef rmb::SymForceArgs A;
-  const SymKernel k = f32 ? sym_force32(radii != nullptr)
+  const SymKernel k = body ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false, rmb::BodyYukawaLaw>>(0)
+                                       : sym_kernel_of<A, rmb::sym_force_kernel<false, false, rmb::BodyYukawaLaw>>(0))
+                      : f32 ? sym_force32(radii != nullptr)
                           : radii ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, true>>(0) : sym_kernel_of<A, rmb::sym_force_kernel<false, true>>(0))
                                   : (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false>>(0) : sym_kernel_of<A, rmb::sym_force_kernel<false, false>>(0));
   long blocks;

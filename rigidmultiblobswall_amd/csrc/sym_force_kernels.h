@@ -1,8 +1,9 @@
-// sym_force_kernels.h -- symmetric blob-blob force sweep (gfx950, fp64).
+// sym_force_kernels.h -- symmetric pair-force sweep (gfx950, fp64): blob-blob forces and body-body forces.
 //
 // F_ij = -F_ji, so each unordered pair is evaluated once (one rsqrt + one exp) and applied with opposite signs.  Same
 // tile-pair rotation, LDS accumulation and static step schedule (sym_schedule.h) as sym_kernel; tile culling by the
-// range of the exponential.  multi_bodies/forces_numba.py:12-55 semantics.
+// range of the exponential.  The pair law is a policy of the one frame: BlobContactLaw (multi_bodies/forces_numba.py:12-55
+// semantics) or BodyYukawaLaw (multi_bodies_functions.py:359-384, a Yukawa repulsion between body locations).
 #pragma once
 #include "pair_ops.h"
 #include "sym_schedule.h"
@@ -32,11 +33,39 @@ struct SymForceArgs {
   // Spatially sorted configuration (rmb_sort.hip): `pos` is then the sorted copy and perm[s] the caller's index of
   // sorted slot s; the finalize kernel writes slot s to out[perm[s]].  nullptr = the caller's order.
   const unsigned* perm;
+  double eps;           // BodyYukawaLaw: the strength itself (eps_over_b serves both laws)
 };
 
-// f0(r) dr for one pair; dr = r_j - r_i (minimal image), two_a = contact distance of the pair.
+// Pair laws: f0 with (force ON i) = f0 dr, dr = r_j - r_i; r = |dr| and ir = 1/r come from the frame (one rsqrt per pair).
+// Padding lanes sit 2e100 apart from everything: exp_nonpositive returns exactly 0 there, and so does every law.
+//
+// Blob-blob contact law, two_a = contact distance of the pair:
+//   far: -(eps/b) exp(-(r-2a)/b) / r ;  near (r <= 2a): -(eps/b) / max(r, 1e-25) = -(eps/b) min(1/r, 1e25)
+// Branch-free: x = min((2a - r)/b, 0) is 0 exactly for r <= 2a (and for r = NaN at coincident points, fmin keeps
+// the number), exp(0) = 1 exactly, and min(1/r, 1e25) = 1/r for every r > 2a -- one expression serves both ranges.
+struct BlobContactLaw {
+  static __device__ __forceinline__ double f0(const SymForceArgs& a, double two_a, double r, double ir) {
+    const double x = fmin((two_a - r) * a.inv_b, 0.0);
+    const double e = exp_nonpositive(a.ec, x);
+    return -a.eps_over_b * (e * fmin(ir, 1e25));
+  }
+};
+
+// Body-body Yukawa law, U = eps exp(-r/b) / r between body locations (multi_bodies_functions.py:383):
+//   F_on_i = -(eps/b + eps/r) exp(-r/b) dr / r^2 ,  no contact distance (two_a is unused), no torque.
+// One more multiply by 1/r than the contact law, no division.  Coincident locations (r = 0) divide by zero in the
+// reference; here ir is not finite then, fmin keeps the exponent a number, and the two bodies of that pair -- no
+// others -- get non-finite sums.
+struct BodyYukawaLaw {
+  static __device__ __forceinline__ double f0(const SymForceArgs& a, double, double r, double ir) {
+    const double e = exp_nonpositive(a.ec, fmin(-r * a.inv_b, 0.0));
+    return -__builtin_fma(a.eps, ir, a.eps_over_b) * (e * (ir * ir));
+  }
+};
+
+// LAW::f0(r) dr for one pair; dr = r_j - r_i (minimal image in every direction with L > 0).
 // Returns the force ON i; the force on j is minus it.
-template <bool PERIODIC>
+template <bool PERIODIC, class LAW>
 __device__ __forceinline__ void pair_force(const SymForceArgs& a, double two_a, double dx, double dy, double dz, double& fx,
                                            double& fy, double& fz) {
   if constexpr (PERIODIC) {
@@ -47,16 +76,11 @@ __device__ __forceinline__ void pair_force(const SymForceArgs& a, double two_a, 
   const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
   const double ir = rsqrt_f64(r2);
   const double r = r2 * ir;
-  // far: -(eps/b) exp(-(r-2a)/b) / r ;  near (r <= 2a): -(eps/b) / max(r, 1e-25) = -(eps/b) min(1/r, 1e25)
-  // Branch-free: x = min((2a - r)/b, 0) is 0 exactly for r <= 2a (and for r = NaN at coincident points, fmin keeps
-  // the number), exp(0) = 1 exactly, and min(1/r, 1e25) = 1/r for every r > 2a -- one expression serves both ranges.
-  const double x = fmin((two_a - r) * a.inv_b, 0.0);
-  const double e = exp_nonpositive(a.ec, x);
-  const double f0 = -a.eps_over_b * (e * fmin(ir, 1e25));
+  const double f0 = LAW::f0(a, two_a, r, ir);
   fx = f0 * dx; fy = f0 * dy; fz = f0 * dz;
 }
 
-template <bool PERIODIC, bool RADII = false>
+template <bool PERIODIC, bool RADII = false, class LAW = BlobContactLaw>
 __global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForceArgs a) {
   __shared__ double4 rec_all[kSymWaves][64];
   __shared__ double accj_all[kSymWaves][3 * 64];
@@ -127,7 +151,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForc
       const int jj = (lane + k) & 63;
       const double4 q = rec[jj];
       double fx, fy, fz;
-      pair_force<PERIODIC>(a, RADII ? ri + q.w : a.two_a, q.x - xi, q.y - yi, q.z - zi, fx, fy, fz);
+      pair_force<PERIODIC, LAW>(a, RADII ? ri + q.w : a.two_a, q.x - xi, q.y - yi, q.z - zi, fx, fy, fz);
       ax += fx; ay += fy; az += fz;
       if (!diag) {   // wave-uniform
         // the LDS slab collects +f (ds_add_f64 has no negate modifier: -f would cost a v_xor + v_mov per component

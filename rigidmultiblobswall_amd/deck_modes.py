@@ -6,6 +6,14 @@ The reference picks its backends by strings (multi_bodies/multi_bodies.py:207-28
 physics and is ignored; the SUFFIX does (`_no_wall`, `_free_surface`, `radii_*`), and so do per-blob radii in a
 4-column .vertex file.  A deck that asks for a mode the time steppers here do not run must fail loudly: silently
 running it with a wall, a uniform radius or without the body-body forces would be different physics.
+
+`body_body_force_torque_implementation`: `None`, or `python` / `hip` -- the same Yukawa repulsion between body locations
+(multi_bodies_functions.py:359-408), run as one symmetric HIP sweep over the centres.  It needs a context that has the
+sweep (a single-GPU MobilityContext): the caller says so through validate(..., body_body_forces=True); on any other
+context the deck is refused.  Rigid decks follow the reference's driver (force_torque_calculator_sort_by_bodies adds the
+term, :443).  The reference's roller integrator builds its forces from calc_one_blob_forces + calc_blob_blob_forces alone
+(quaternion_integrator_rollers.py:930-933) and never evaluates the option; a roller deck here adds the law the option
+names to every force evaluation, which is that integrator with the law in its pair-force hook.
 """
 import numpy as np
 
@@ -43,7 +51,7 @@ def hydrodynamic_mode(impl, option, free_surface=False):
   raise ValueError("%s %r: unknown implementation suffix %r" % (option, impl, suffix))
 
 
-def validate(read, uses_dense_blocks=True):
+def validate(read, uses_dense_blocks=True, body_body_forces=False):
   """Checks every implementation option of a ReadInput deck against `domain`; returns the hydrodynamic mode
   ('single_wall', 'no_wall' or 'in_plane' as given by `domain`, or 'free_surface': a rigid deck whose product is a
   `<backend>_free_surface` one under `domain single_wall`, multi_bodies.py:262-265).
@@ -55,7 +63,10 @@ def validate(read, uses_dense_blocks=True):
 
   `domain free_surface` is this engine's own spelling, for roller decks (uses_dense_blocks = False) only: the rotational
   blocks of the mirror-image system (context option "free_surface_rotation", beyond the reference).  It requires a
-  `<backend>_free_surface` product and returns 'free_surface'; rigid decks keep the reference's spelling."""
+  `<backend>_free_surface` product and returns 'free_surface'; rigid decks keep the reference's spelling.
+
+  body_body_forces: the caller's context serves the body-body force sweep (hasattr(ctx, "body_body_force_device"));
+  without it a deck with `body_body_force_torque_implementation` other than `None` is refused."""
   domain = read.domain
   if domain == "free_surface":
     if uses_dense_blocks:
@@ -66,7 +77,7 @@ def validate(read, uses_dense_blocks=True):
     if "radii" in impl or _split(impl)[0] is None or _split(impl)[1] != "free_surface":
       raise ValueError("mobility_vector_prod_implementation %r: `domain free_surface` needs a <backend>_free_surface "
                        "product" % (impl,))
-    _check_forces(read)
+    _check_forces(read, body_body_forces)
     return "free_surface"
   if domain not in ("single_wall", "no_wall", "in_plane"):
     raise ValueError("domain %r: expected single_wall, no_wall or in_plane" % (domain,))
@@ -100,11 +111,11 @@ def validate(read, uses_dense_blocks=True):
       raise ValueError("%s %r is a %s implementation but the deck says `domain %s`: the reference would mix an unbounded "
                        "mobility with wall checks (or the reverse); state the intended one"
                        % (option, getattr(read, option), mode, domain))
-  _check_forces(read)
+  _check_forces(read, body_body_forces)
   return domain
 
 
-def _check_forces(read):
+def _check_forces(read, body_body_forces=False):
   """The force options of a deck the time steppers can honour, or a ValueError."""
   ff = read.blob_blob_force_implementation
   if "radii" in ff:
@@ -113,9 +124,12 @@ def _check_forces(read):
   if ff != "None" and _split(ff)[0] is None and ff != "tree_numba":
     raise ValueError("blob_blob_force_implementation %r: unknown implementation string" % (ff,))
   bb = read.body_body_force_torque_implementation
-  if bb != "None":
-    raise ValueError("body_body_force_torque_implementation %r: body-body forces (multi_bodies_functions.py:359-395, a Yukawa "
-                     "potential between body centres) are not built; only `None`" % (bb,))
+  if bb not in ("None", "python", "hip"):
+    raise ValueError("body_body_force_torque_implementation %r: unknown implementation string (None, python or hip)" % (bb,))
+  if bb != "None" and not body_body_forces:
+    raise ValueError("body_body_force_torque_implementation %r: body-body forces (multi_bodies_functions.py:359-408, a Yukawa "
+                     "potential between body centres) run on a single-GPU MobilityContext; this context does not serve the "
+                     "sweep" % (bb,))
 
 
 def free_surface_blocks(read):

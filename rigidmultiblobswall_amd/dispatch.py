@@ -4,6 +4,7 @@ The reference selects implementations by strings from the input deck:
   mobility_vector_prod_implementation -> multi_bodies/multi_bodies.py:233-287
   blob_blob_force_implementation      -> multi_bodies/multi_bodies_functions.py:249-278
   mobility_blobs_implementation       -> multi_bodies/multi_bodies.py:207-230
+  body_body_force_torque_implementation -> multi_bodies/multi_bodies_functions.py:348-356
 These functions add the `hip*` strings and return callables with the reference's signatures.  With
 `accept_reference_gpu_names=True` the reference's own GPU strings (`pycuda`, `pycuda_no_wall`) are
 served by the HIP engine too, so an existing deck runs unchanged.
@@ -64,6 +65,21 @@ def set_blob_blob_forces(implementation, accept_reference_gpu_names=False, *args
     return partial(_forces.calc_blob_blob_forces_radii_hip, radius_blobs=_radius_blobs(kwargs))
   if implementation not in table:
     raise ValueError("blob_blob_force_implementation %r is not served by the HIP engine" % (implementation,))
+  return table[implementation]
+
+
+def _zero_bodies(bodies, r_vectors, *args, **kwargs):
+  return np.zeros((2 * len(bodies), 3))
+
+
+def set_body_body_forces_torques(implementation, *args, **kwargs):
+  """f(bodies, r_vectors, **kwargs) -> (2 N_b, 3): `None`, `hip`, and the reference's own `python` served by the HIP sweep
+  (the same law; multi_bodies_functions.py:348-408)."""
+  table = {"None": _zero_bodies, "hip": _forces.calc_body_body_forces_torques_hip}
+  table["python"] = table["hip"]
+  if implementation not in table:
+    raise ValueError("body_body_force_torque_implementation %r is not served by the HIP engine (known: %s)" %
+                     (implementation, ", ".join(sorted(table))))
   return table[implementation]
 
 

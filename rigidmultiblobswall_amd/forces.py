@@ -6,6 +6,11 @@ Replaces multi_bodies/forces_pycuda.py:148-180 (float32 CUDA) and its CPU twins
                             debye_length=b, blob_radius=a) -> ndarray (N,3)
 selected in the reference by `blob_blob_force_implementation`
 (multi_bodies/multi_bodies_functions.py:249-278).  fp64 here; minimal image only.
+
+Body-body forces (`body_body_force_torque_implementation python`, multi_bodies_functions.py:359-408) behind the
+reference's call as well:
+  calc_body_body_forces_torques_hip(bodies, r_vectors, periodic_length=L, repulsion_strength=eps,
+                                    debye_length=b) -> ndarray (2 N_b, 3), rows [f_0, t_0, f_1, t_1, ...]
 """
 import numpy as np
 
@@ -75,3 +80,22 @@ def calc_blob_blob_forces_radii_hip(r_vectors, radius_blobs, *args, **kwargs):
   ctx = _context(0)      # per-blob radii: one device
   ctx.set_positions(r_vectors, 1.0, L, wall=False)
   return ctx.blob_blob_force_radii(radius_blobs, kwargs.get('repulsion_strength'), kwargs.get('debye_length'))
+
+
+def calc_body_body_forces_torques_hip(bodies, r_vectors, *args, **kwargs):
+  """`calc_body_body_forces_torques_python` (multi_bodies_functions.py:387-408) on the device: a Yukawa repulsion between
+  the bodies' `location`s, one symmetric fp64 sweep over the N_b centres instead of the Python double loop.  Returns
+  (2 N_b, 3): force rows from the kernel, torque rows zero (the reference's law has no torque).  r_vectors is not read,
+  as in the reference."""
+  L = kwargs.get('periodic_length')
+  if L is None:
+    L = np.zeros(3)
+  nb = len(bodies)
+  out = np.zeros((2 * nb, 3))
+  if nb == 0:
+    return out
+  centres = np.array([np.asarray(b.location, dtype=np.float64).reshape(3) for b in bodies])
+  ctx = _context(0)      # the sweep over body centres runs on one device
+  ctx.set_positions(centres, 1.0, L, wall=False)
+  out[0::2] = ctx.body_body_force(kwargs.get('repulsion_strength'), kwargs.get('debye_length'))
+  return out

@@ -141,6 +141,9 @@ class RigidIntegrator(object):
     self.debye_length_wall = 1.0
     self.repulsion_strength = 0.0
     self.debye_length = 1.0
+    # body-body forces (multi_bodies_functions.py:359-408): None, or (repulsion_strength, debye_length) of the Yukawa
+    # repulsion between body locations -- one more symmetric sweep, over the nb centres
+    self.body_body_force = None
     # hooks, as the reference's attributes of the same names (tensors in / out)
     self.calc_slip = None                       # callable(integrator) -> (Nblobs, 3) tensor
     self.slip_body_frame = None                 # (Nblobs, 3) tensor: constant active slip in the body frame (.slip files)
@@ -257,11 +260,28 @@ class RigidIntegrator(object):
       ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
     return f
 
+  def _body_body_forces(self):
+    """(nb, 3) Yukawa forces between the body locations of the bound configuration -- the one the blob forces of this
+    call see; the reference reads `b.location`, which the schemes move to the midpoint / RFD point before they solve
+    (multi_bodies_functions.py:387-408; the law has no torque).  The nb centres become the context's resident points for
+    one sweep (raw coordinates, no clamp), then the mobility view is restored, as _blob_forces does."""
+    eps, b = self.body_body_force
+    ctx = self.susp.ctx
+    if not hasattr(ctx, "body_body_force_device"):
+      raise ValueError("body-body forces need a single-GPU MobilityContext; %s does not serve the sweep" % type(ctx).__name__)
+    ctx.set_positions(self.susp.location.contiguous().view(-1), self.a, self.periodic_length, False)
+    f = ctx.body_body_force_device(eps, b).view(-1, 3)
+    ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)   # back to the mobility view
+    return f
+
   def force_torque_calculator(self):
     """(nb, 6) force and torque on every body from the blob forces: F = sum f, T = sum rel x f = K^T f
-    (multi_bodies_functions.py:411-445), plus the optional external hook."""
+    (multi_bodies_functions.py:411-445), plus the body-body forces (`body_body_force`) and the optional external hook."""
     f = self.calc_blob_forces(self.susp.r_dev.view(-1, 3))
     FT = self.susp.KT_times_lambda(f.reshape(-1)).view(-1, 6)
+    if self.body_body_force is not None:
+      FT = FT.clone()
+      FT[:, 0:3] += self._body_body_forces()
     if self.external_force_torque is not None:
       FT = FT + self.external_force_torque(self)
     return FT
@@ -822,7 +842,9 @@ def bodies_from_input(read):
 def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   """Integrator wired from a ReadInput deck as multi_bodies/multi_bodies.py:1319-1393 wires QuaternionIntegrator."""
   from . import deck_modes
-  domain = deck_modes.validate(read, uses_dense_blocks=True)     # ValueError for modes this engine does not run
+  # ValueError for modes this engine does not run; body-body forces only where the context has the sweep (a context made
+  # here is a MobilityContext, which does)
+  domain = deck_modes.validate(read, uses_dense_blocks=True, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"))
   phoretic = deck_modes.phoretic(read)                  # ValueError for phoretic modes this engine does not run
   block_boundary = None
   if domain == "free_surface":
@@ -846,6 +868,8 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   if read.blob_blob_force_implementation != "None":
     integ.repulsion_strength = read.repulsion_strength
     integ.debye_length = read.debye_length
+  if read.body_body_force_torque_implementation != "None":     # the same two numbers, as the reference's kwargs
+    integ.body_body_force = (read.repulsion_strength, read.debye_length)
   if any_slip:
     integ.slip_body_frame = torch.as_tensor(b["slips"], device=integ.device)
   if phoretic:

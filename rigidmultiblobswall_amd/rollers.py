@@ -87,6 +87,9 @@ class RollersIntegrator(object):
     self.debye_length_wall = 1.0
     self.repulsion_strength = 0.0
     self.debye_length = 1.0
+    # body-body forces (multi_bodies_functions.py:359-408): None, or (repulsion_strength, debye_length) of the Yukawa
+    # repulsion between body locations -- the rollers themselves; added to the pair forces of every force evaluation
+    self.body_body_force = None
     # replaceable hooks, as the reference's attributes of the same names; tensors (N,3) in and out
     self.calc_one_blob_forces = self._one_blob_forces
     self.calc_blob_blob_forces = self._blob_blob_forces
@@ -222,10 +225,20 @@ class RollersIntegrator(object):
     return f
 
   def _blob_blob_forces(self, r):
-    if self.repulsion_strength == 0.0:
+    """Pair forces at r: the blob-blob repulsion, plus the body-body Yukawa force (`body_body_force`; a roller is a body,
+    its location the blob's) as a second sweep over the positions the first one made resident."""
+    if self.repulsion_strength == 0.0 and self.body_body_force is None:
       return torch.zeros_like(r)
     self._bind(r, wall=False)    # forces act on the true heights, not the clamped ones
-    return self.ctx.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a).view(-1, 3)
+    f = None
+    if self.repulsion_strength != 0.0:
+      f = self.ctx.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a).view(-1, 3)
+    if self.body_body_force is not None:
+      if not hasattr(self.ctx, "body_body_force_device"):
+        raise ValueError("body-body forces need a single-GPU MobilityContext; %s does not serve the sweep" % type(self.ctx).__name__)
+      fb = self.ctx.body_body_force_device(*self.body_body_force).view(-1, 3)
+      f = fb if f is None else f + fb
+    return f
 
   def get_omega_one_roller(self):
     return np.asarray(self.omega_one_roller, dtype=np.float64)
@@ -627,7 +640,9 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   random numbers are numpy's stream for that seed (the reference calls np.random.seed, :1157-1158)."""
   from . import deck_modes
   from . import structures as st
-  domain = deck_modes.validate(read, uses_dense_blocks=False)    # ValueError for modes this engine does not run
+  # ValueError for modes this engine does not run; body-body forces only where the context has the sweep (a context made
+  # here is a MobilityContext, which does)
+  domain = deck_modes.validate(read, uses_dense_blocks=False, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"))
   deck_modes.phoretic(read)                             # ValueError for .Laplace files
   locations = []
   body_types = []
@@ -655,6 +670,8 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   if read.blob_blob_force_implementation != "None":
     integ.repulsion_strength = read.repulsion_strength
     integ.debye_length = read.debye_length
+  if read.body_body_force_torque_implementation != "None":     # the same two numbers, as the reference's kwargs
+    integ.body_body_force = (read.repulsion_strength, read.debye_length)
   integ.periodic_length = np.asarray(read.periodic_length, dtype=np.float64)
   integ.omega_one_roller = np.asarray(read.omega_one_roller, dtype=np.float64)
   integ.free_kinematics = read.free_kinematics
