@@ -439,6 +439,39 @@ int rmb_blob_potential_device(rmb_ctx* ctx, double repulsion_strength, double de
 int rmb_mcmc_propose_device(rmb_ctx* ctx, long n_bodies, long n_free, long n_blobs, const int* blob_body_dev, const int* blob_ref_dev,
                             const double* ref_dev, const double* loc_dev, const double* quat_dev, const double* draws_dev,
                             double max_angle_shift, double* loc_new_dev, double* quat_new_dev, double* r_new_dev);
+/* Single-body Metropolis moves.  E(r) = sum_i u1(z_i) + sum_{i<j, z_i>0} u2(r_ij) is rmb_blob_potential's energy (same forms,
+ * same rule behind the wall, minimal image in x and y only, same r = 0 behaviour, fp64).  A body owns the contiguous blob
+ * range [first, first + count) of r_dev (n_blobs x 3 raw coordinates, the caller's -- NOT the resident configuration, which
+ * is neither read nor changed; periodic_length: 3 doubles on the host, [2] ignored).  With r' = r except for that range,
+ * where it is r_body_new_dev (count x 3):
+ *   out_dev = {U_one(r') - U_one(r), U_pair(r') - U_pair(r)}
+ * as a sum over the touched terms, each subtracted (new - old) before it is accumulated: a pair with j < first is gated by
+ * z_j > 0 (unchanged by the move), a pair with j >= first + count or with both blobs in the body (once, i < j) by z'_i > 0
+ * for the new term and z_i > 0 for the old one.  One lane per blob of the configuration, the body staged in LDS 256 blobs at
+ * a time (any count), one pair of partials per wave, a finishing launch that adds them in a fixed order: O(count n_blobs),
+ * no atomics, bit-reproducible.  Asynchronous on the context's stream.  RMB_ERR_ARG: a null pointer, an empty or
+ * out-of-range blob range, debye_length <= 0 (debye_length_wall <= 0 with a wall term), an unknown form. */
+int rmb_mcmc_body_delta_device(rmb_ctx* ctx, long n_blobs, const double* r_dev, long first, long count, const double* r_body_new_dev,
+                               const double* periodic_length, double repulsion_strength, double debye_length,
+                               double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
+                               double* out_dev);
+/* One sweep of single-body moves over bodies 0 ... n_free - 1 in index order, inside the library.  Body k owns the blobs
+ * [body_first[k], body_first[k + 1]) (host table of n_bodies + 1 entries from 0 to n_blobs, non-decreasing: anything else is
+ * RMB_ERR_ARG).  Per body two launches: the first composes the proposal from draws_dev[k, 0:3] (displacement) and
+ * draws_dev[k, 3:6] (rotation vector / max_angle_shift) with the arithmetic of rmb_mcmc_propose_device and computes the
+ * difference above on r_dev; the finishing launch (one workgroup) adds the partials and decides
+ *   draws_dev[k, 6] < exp(-(dU_one + dU_pair) / kT)      (numpy's comparison: a NaN rejects, -inf accepts).
+ * On acceptance it commits in place the body's rows of r_dev, loc_dev[k], quat_dev[k] and energy_dev = {U_one, U_pair} (the
+ * running energy: the caller initialises it, e.g. with rmb_blob_potential_device) and sets accepted_dev[k] = 1; on rejection it
+ * writes accepted_dev[k] = 0 and nothing else.  draws_dev is (n_free, 7); bodies from n_free on are never moved.  No host
+ * synchronisation and no copy command between moves: the caller reads accepted_dev and energy_dev after the call
+ * (asynchronous on the context's stream).  With option "timing" the events bracket the whole sweep.  n_free = 0 is a no-op;
+ * RMB_ERR_ARG also for a null pointer, kT <= 0, debye_length <= 0 (debye_length_wall <= 0 with a wall term). */
+int rmb_mcmc_sweep_device(rmb_ctx* ctx, long n_bodies, long n_free, long n_blobs, const long* body_first, const int* blob_ref_dev,
+                          const double* ref_dev, double* loc_dev, double* quat_dev, double* r_dev, const double* draws_dev,
+                          double max_angle_shift, const double* periodic_length, double repulsion_strength, double debye_length,
+                          double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
+                          double kT, double* energy_dev, int* accepted_dev);
 /* One-blob forces of the rigid-multiblob driver (multi_bodies/multi_bodies_functions.py:153-188, `blob_external_force`):
  * f = (0, 0, -weight + wall repulsion), wall repulsion = (eps_wall / debye_wall) exp(-(h - a) / debye_wall) above contact
  * (h > a), eps_wall / debye_wall below; r_dev: n x 3 raw coordinates (the caller's, not the resident ones); accumulate != 0

@@ -568,6 +568,62 @@ class MobilityContext(object):
     _lib.check(self._lib.rmb_mcmc_propose_device(self._h, nb, int(n_free), n_blobs, p(blob_body), p(blob_ref), p(ref), p(loc), p(quat), p(draws),
                                                  float(max_angle_shift), p(loc_new), p(quat_new), p(r_new)))
 
+  def mcmc_body_delta_device(self, r, first, count, body_new, periodic_length, repulsion_strength, debye_length, blob_radius,
+                             repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0, potential="soft", out=None):
+    """{U_one(r') - U_one(r), U_pair(r') - U_pair(r)} as a CUDA float64 tensor of two entries, r' = r (n x 3 CUDA tensor, the
+    caller's coordinates -- the resident configuration is not involved) with the rows [first, first + count) replaced by
+    body_new (count x 3): rmb_mcmc_body_delta_device, asynchronous on the context's stream."""
+    import torch
+    args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
+    for name, t in (("r", r), ("body_new", body_new)):
+      if not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() % 3:
+        raise ValueError("%s must be a contiguous CUDA float64 tensor of (rows, 3)" % name)
+    n, first, count = r.numel() // 3, int(first), int(count)
+    if not (0 <= first and 0 < count and first + count <= n) or body_new.numel() != 3 * count:
+      raise ValueError("the body's blob range [first, first + count) must lie inside r and body_new must have count rows")
+    if out is None:
+      out = torch.empty(2, dtype=torch.float64, device=r.device)
+    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2:
+      raise ValueError("out must be a contiguous CUDA float64 tensor with 2 entries")
+    L = _as_f64(np.zeros(3) if periodic_length is None else periodic_length, 3)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_mcmc_body_delta_device(self._h, n, ctypes.c_void_p(r.data_ptr()), first, count, ctypes.c_void_p(body_new.data_ptr()),
+                                                    _ptr(L), *args, ctypes.c_void_p(out.data_ptr())))
+    return out
+
+  def mcmc_sweep_device(self, body_first, blob_ref, ref, loc, quat, r, draws, n_free, max_angle_shift, periodic_length, kT, energy, accepted,
+                        repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0,
+                        potential="soft"):
+    """One sweep of single-body Metropolis moves over bodies 0 ... n_free - 1, decided and committed on the device
+    (rmb_mcmc_sweep_device): loc, quat, r (current blob coordinates) and energy = {U_one, U_pair} (running) are updated in
+    place, accepted[k] (int32) is the flag of move k; draws is (n_free, 7).  body_first: host table of n_bodies + 1 blob
+    offsets.  Asynchronous on the context's stream: read the flags and the energy afterwards."""
+    import torch
+    args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
+    body_first = np.ascontiguousarray(body_first, dtype=np.int64).reshape(-1)
+    nb, n_blobs, n_free = loc.numel() // 3, r.numel() // 3, int(n_free)
+    if body_first.size != nb + 1 or not 0 <= n_free <= nb:
+      raise ValueError("body_first must have n_bodies + 1 entries and 0 <= n_free <= n_bodies")
+    if not (isinstance(blob_ref, torch.Tensor) and blob_ref.is_cuda and blob_ref.dtype == torch.int32 and blob_ref.is_contiguous()):
+      raise ValueError("blob_ref must be a contiguous CUDA int32 tensor")
+    if not (isinstance(accepted, torch.Tensor) and accepted.is_cuda and accepted.dtype == torch.int32 and accepted.is_contiguous()):
+      raise ValueError("accepted must be a contiguous CUDA int32 tensor")
+    for name, t in (("ref", ref), ("loc", loc), ("quat", quat), ("r", r), ("draws", draws), ("energy", energy)):
+      if not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous CUDA float64 tensor" % name)
+    sizes = (("blob_ref", blob_ref, n_blobs, False), ("loc", loc, 3 * nb, False), ("quat", quat, 4 * nb, False), ("r", r, 3 * n_blobs, False),
+             ("draws", draws, 7 * n_free, True), ("energy", energy, 2, False), ("accepted", accepted, n_free, True))
+    for name, t, size, at_least in sizes:
+      if t.numel() < size or (not at_least and t.numel() != size):
+        raise ValueError("%s must have %d entries, has %d" % (name, size, t.numel()))
+    if ref.numel() % 3:
+      raise ValueError("ref must be (rows, 3)")
+    L = _as_f64(np.zeros(3) if periodic_length is None else periodic_length, 3)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_mcmc_sweep_device(self._h, nb, n_free, n_blobs, _ptr(body_first), p(blob_ref), p(ref), p(loc), p(quat), p(r), p(draws),
+                                               float(max_angle_shift), _ptr(L), *args, float(kT), p(energy), p(accepted)))
+
   def one_blob_force_device(self, r, blob_radius, weight, eps_wall, debye_wall, out=None):
     """(0, 0, -weight + wall repulsion) per blob on the caller's coordinates r (n x 3 CUDA tensor; rmb_one_blob_force_device);
     `out` given = accumulate into it, None = a new tensor."""

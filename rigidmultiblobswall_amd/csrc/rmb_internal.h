@@ -22,6 +22,8 @@
 //                    (host loop native too); one workspace layout for both (krylov_workspace)
 //   rmb_potential.hip  total potential energy of a blob configuration (potential_kernels.h: symmetric sweep to a scalar,
 //                    atomic-free) and the Metropolis proposal of the equilibrium sampler
+//   rmb_mcmc_moves.hip  single-body Metropolis moves (mcmc_move_kernels.h): energy difference of one moved body, and a
+//                    whole sweep of moves decided and committed on the device
 //   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
 //                    points and the two fused device sweeps of the concentration solve
 #pragma once
@@ -82,6 +84,7 @@ struct CtxBuffers {
   // spatially sorted copy of the configuration for the force kernel (rmb_sort.hip): valid together with tile_bounds
   DevBuf fpos, fperm, fsort_keys, fsort_vals, fsort_tmp, fsort_box;
   DevBuf pot_ws;           // potential energy (rmb_potential.hip): per-wave partial sums + the two results
+  DevBuf mcmc_ws;          // single-body moves (rmb_mcmc_moves.hip): per-wave partial differences + the proposed body
   DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
   DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
   DevBuf krylov;   // partial sums of rmb_krylov_orthogonalize_device
@@ -91,7 +94,7 @@ struct CtxBuffers {
 using CB = CtxBuffers;
 constexpr DevBuf CB::* kCtxBufs[] = {&CB::pos, &CB::r_stage, &CB::vec, &CB::vec2, &CB::out, &CB::partial, &CB::tmp3n, &CB::tile_bounds,
                                      &CB::fpos, &CB::fperm, &CB::fsort_keys, &CB::fsort_vals, &CB::fsort_tmp, &CB::fsort_box,
-                                     &CB::pot_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
+                                     &CB::pot_ws, &CB::mcmc_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
 static_assert(sizeof(CtxBuffers) == (sizeof(kCtxBufs) / sizeof(kCtxBufs[0]) + 8) * sizeof(DevBuf),
               "a DevBuf of CtxBuffers is missing from kCtxBufs (or st[] changed its length)");
 template <class Bufs, class F>      // Bufs: CtxBuffers or const CtxBuffers (an rmb_ctx converts)

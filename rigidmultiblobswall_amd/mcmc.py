@@ -1,6 +1,7 @@
 """Metropolis sampler of rigid-body configurations -- many_bodyMCMC/many_body_MCMC.py on MI355X.
 
     python -m rigidmultiblobswall_amd.mcmc [inputfile] [--device N] [--potential soft|yukawa] [--rng reference|batched]
+                                           [--moves all|single]
 
 Same decks, same outputs (.inputfile, .random_state, .clones per saved step or one appended .config, .time, .MCMC_info)
 and, with rng="reference", the same chain as the reference script for the same seed: the draws come from a
@@ -13,6 +14,14 @@ State on the device: body locations, quaternions and the structures' reference c
 uploads one (n_bodies, 6) array of draws, one launch composes the proposal and writes the proposed blob coordinates
 (rmb_mcmc_propose_device), the energy sweep runs (rmb_blob_potential), one pair of doubles comes back; an accepted
 proposal becomes current by swapping the two sets of tensors.
+
+`moves="single"` (beyond the reference, which moves every free body in one proposal): one step of the deck is one SWEEP of
+single-body moves over the free bodies in index order.  Per sweep the host draws, per free body, uniform(-t, t, 3),
+normal(0, 1, 3) and uniform(0, 1) (rng="batched": the three blocks (n, 3), (n, 3), (n,)) and uploads them once as (n_free, 7);
+rmb_mcmc_sweep_device then runs two launches per body -- proposal + energy difference of that body in O(n_body N), decision +
+commit in place -- without a host synchronisation in between, and the host reads the flags and the running energy.  The
+acceptance recursion is applied once per flag, the +-2 % rule once per step; at every save the full energy is recomputed
+(energy_drift) and the running value reset to it.
 
 `MCMCSampler(..., energy=f)` runs the same chain with f(r_vectors) -> float as the energy and numpy state instead (the
 host tests replay the reference's fixtures with the numpy restatement that way); without it the energy is the HIP one --
@@ -89,6 +98,7 @@ class _HostState(object):
   def __init__(self, sampler, energy):
     self.s, self.energy_fn = sampler, energy
     self.loc, self.quat = sampler.loc0.copy(), sampler.quat0.copy()
+    self.running, self.decision_margin = None, np.inf      # moves="single"
 
   def _blobs(self, loc, quat):
     s = self.s
@@ -104,6 +114,35 @@ class _HostState(object):
 
   def accept(self):
     self.loc, self.quat = self.loc_new, self.quat_new
+
+  def sweep(self, draws, max_angle_shift):
+    """One sweep of single-body moves: dE = energy(new) - energy(old) with the caller's function, decided as the all-body
+    step is.  -> (flags, energy after the sweep); decision_margin keeps the smallest |u - exp(-dE/kT)| of the run."""
+    kT = np.float64(self.s.kT)
+    if self.running is None:
+      self.running = np.float64(self.current_energy())
+    flags = []
+    for k in range(self.s.n_free):
+      loc_k, quat_k = compose_proposal(self.loc[k:k + 1], self.quat[k:k + 1], draws[k:k + 1, 0:6], 1, max_angle_shift)
+      loc_new, quat_new = self.loc.copy(), self.quat.copy()
+      loc_new[k], quat_new[k] = loc_k[0], quat_k[0]
+      sample = np.float64(self.energy_fn(self._blobs(loc_new, quat_new)))
+      with np.errstate(over="ignore", invalid="ignore"):
+        bound = np.exp(-(sample - self.running) / kT)
+        ok = bool(draws[k, 6] < bound)
+        margin = abs(draws[k, 6] - bound)
+      if margin < self.decision_margin:        # a NaN bound compares false: it rejects, and no rounding changes that
+        self.decision_margin = float(margin)
+      flags.append(ok)
+      if ok:
+        self.loc, self.quat, self.running = loc_new, quat_new, sample
+    return flags, float(self.running)
+
+  def recompute_energy(self):
+    """The full energy of the current configuration; the running value becomes it.  -> (running before, full)"""
+    before = self.running
+    self.running = np.float64(self.current_energy())
+    return float(self.running if before is None else before), float(self.running)
 
   def configuration(self):
     return self.loc, self.quat
@@ -129,6 +168,43 @@ class _DeviceState(object):
     self.r_new = torch.empty((sampler.n_blobs, 3), dtype=torch.float64, device=self.dev)
     self.draws_host = torch.zeros((sampler.n_bodies, 6), dtype=torch.float64).pin_memory()
     self.draws = torch.zeros((sampler.n_bodies, 6), dtype=torch.float64, device=self.dev)
+    if sampler.moves == "single":
+      # r_new holds the CURRENT blob coordinates between sweeps: the finishing launch of an accepted move rewrites its rows
+      self.body_first = np.ascontiguousarray(sampler.body_first, dtype=np.int64)
+      self.draws7_host = torch.zeros((max(sampler.n_free, 1), 7), dtype=torch.float64).pin_memory()
+      self.draws7 = torch.zeros((max(sampler.n_free, 1), 7), dtype=torch.float64, device=self.dev)
+      self.energy = torch.zeros(2, dtype=torch.float64, device=self.dev)        # running {U_one, U_pair}
+      self.flags = torch.zeros(max(sampler.n_free, 1), dtype=torch.int32, device=self.dev)
+
+  def _energy_terms(self, out=None):
+    s = self.s
+    with self.torch.cuda.device(self.dev):
+      self.ctx.set_positions(self.r_new, s.blob_radius, s.periodic_length, wall=False)
+      return self.ctx.blob_potential_device(s.repulsion_strength, s.debye_length, s.blob_radius,
+                                            repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
+                                            weight=s.weight, potential=s.potential, out=out)
+
+  def recompute_energy(self):
+    """The full energy of the current coordinates (the energy sweep); the running pair on the device becomes it.
+    -> (running before, full)"""
+    before = float(self.energy.sum().item())
+    self._energy_terms(out=self.energy)
+    return before, float(self.energy.sum().item())
+
+  def sweep(self, draws, max_angle_shift):
+    """One sweep of single-body moves (rmb_mcmc_sweep_device).  -> (flags, running energy after the sweep)"""
+    s = self.s
+    if s.n_free == 0:
+      return [], float(self.energy.sum().item())
+    self.draws7_host.numpy()[...] = draws[:s.n_free]
+    self.draws7.copy_(self.draws7_host, non_blocking=True)
+    with self.torch.cuda.device(self.dev):
+      self.ctx.mcmc_sweep_device(self.body_first, self.blob_ref, self.ref, self.loc, self.quat, self.r_new, self.draws7, s.n_free,
+                                 max_angle_shift, s.periodic_length, s.kT, self.energy, self.flags, s.repulsion_strength, s.debye_length,
+                                 s.blob_radius, repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
+                                 weight=s.weight, potential=s.potential)
+    flags = self.flags[:s.n_free].cpu().numpy()
+    return [bool(f) for f in flags], float(self.energy.sum().item())
 
   def _energy(self):
     s = self.s
@@ -146,6 +222,8 @@ class _DeviceState(object):
 
   def current_energy(self):
     self._propose(self.loc, self.quat, 0, 0.0)       # no free body: the current configuration's blob coordinates
+    if self.s.moves == "single":
+      return self.recompute_energy()[1]
     return self._energy()
 
   def upload(self, draws):
@@ -174,16 +252,24 @@ class _DeviceState(object):
 class MCMCSampler(object):
   """many_body_MCMC.py:100-304.  `read`: a ReadInput (or the path of a deck).  After run(): energy_log (the start energy,
   then every proposal's), accepted (one bool per step), accepted_moves, max_translation, max_angle_shift, and -- with
-  keep_saved (default: only when no files are written) -- saved: step -> (locations, quaternions) of every save."""
+  keep_saved (default: only when no files are written) -- saved: step -> (locations, quaternions) of every save.
+  moves="single": a step is one sweep of single-body moves over the free bodies; accepted holds one bool per MOVE,
+  accepted_moves counts moves, energy_log the start energy and the running energy after every sweep, energy_drift: step ->
+  (running energy, recomputed full energy) of every save."""
 
   def __init__(self, read, device=0, potential="soft", rng="reference", energy=None, write_files=True, verbose=False,
-               check_user_potential=True, keep_saved=None):
+               check_user_potential=True, keep_saved=None, moves="all"):
     if check_user_potential:
       refuse_user_defined_potential(".")
     if potential not in ("soft", "yukawa"):
       raise ValueError("potential must be 'soft' or 'yukawa', got %r" % (potential,))
     if rng not in ("reference", "batched"):
       raise ValueError("rng must be 'reference' or 'batched', got %r" % (rng,))
+    if moves not in ("all", "single"):
+      raise ValueError("moves must be 'all' or 'single', got %r" % (moves,))
+    if moves == "single" and energy is None and not isinstance(device, (int, np.integer)):
+      raise ValueError("moves='single' takes a device index, not %r" % (device,))
+    self.moves = moves
     self.read = read = ReadInput(read) if isinstance(read, str) else read
     self.potential, self.rng_mode, self.write_files, self.verbose = potential, rng, write_files, verbose
     if read.n_steps <= read.initial_step:
@@ -216,12 +302,14 @@ class MCMCSampler(object):
     self.quat0 = np.concatenate(quats).reshape(-1, 4)
     self.blob_body = np.concatenate(blob_body).astype(np.int64)
     self.blob_ref = np.concatenate(blob_ref).astype(np.int64)
+    # body k owns the blobs [body_first[k], body_first[k + 1])
+    self.body_first = np.concatenate([[0], np.cumsum(np.bincount(self.blob_body, minlength=body0))]).astype(np.int64)
     self.n_bodies, self.n_free, self.n_blobs = body0, n_free, self.blob_body.size
     self.max_body_length = max_len
     self.max_translation = self.blob_radius * 0.1
     self.max_angle_shift = self.max_translation / self.max_body_length
     self.accepted_moves, self.acceptance_ratio = 0, 0.5
-    self.energy_log, self.accepted, self.saved = [], [], {}
+    self.energy_log, self.accepted, self.saved, self.energy_drift = [], [], {}, {}
     # saved configurations stay in memory only when asked for, or when no file receives them
     self.keep_saved = (not write_files) if keep_saved is None else bool(keep_saved)
     self.draw_seconds = 0.0
@@ -243,8 +331,25 @@ class MCMCSampler(object):
       d[:self.n_free, 3:6] = rng.normal(0, 1, (self.n_free, 3))
     return d
 
+  def _sweep_draws(self, rng):
+    """(n_free, 7) of one sweep: displacement, rotation vector / max_angle_shift, the uniform of the decision."""
+    d = np.zeros((self.n_free, 7))
+    t = self.max_translation
+    if self.rng_mode == "reference":
+      for k in range(self.n_free):
+        d[k, 0:3] = rng.uniform(-t, t, 3)
+        d[k, 3:6] = rng.normal(0, 1, 3)
+        d[k, 6] = rng.uniform(0.0, 1.0)
+    else:
+      d[:, 0:3] = rng.uniform(-t, t, (self.n_free, 3))
+      d[:, 3:6] = rng.normal(0, 1, (self.n_free, 3))
+      d[:, 6] = rng.uniform(0.0, 1.0, self.n_free)
+    return d
+
   # ---- output ------------------------------------------------------------------------------------------------------------
   def _save(self, step):
+    if self.moves == "single":      # the running energy against a full evaluation, which it then restarts from
+      self.energy_drift[step] = self.state.recompute_energy()
     loc, quat = self.state.configuration()
     if self.keep_saved:
       self.saved[step] = (np.array(loc), np.array(quat))
@@ -264,6 +369,11 @@ class MCMCSampler(object):
       offset += self.body_types[i]
 
   def info_lines(self, last_step):
+    if self.moves == "single":      # per move
+      return ["acceptance ratio = " + str(self.accepted_moves / max(1.0, float(len(self.accepted)))),
+              "accepted_moves = " + str(self.accepted_moves),
+              "final max_translation = " + str(self.max_translation),
+              "final max_angle_shift = " + str(self.max_angle_shift)]
     return ["acceptance ratio = " + str(self.accepted_moves / (last_step + 2.0 - self.read.initial_step)),
             "accepted_moves = " + str(self.accepted_moves),
             "final max_translation = " + str(self.max_translation),
@@ -283,20 +393,28 @@ class MCMCSampler(object):
     step = read.initial_step
     for step in range(read.initial_step, read.n_steps):
       t0 = time.perf_counter()
-      draws = self._draws(rng)
+      draws = self._sweep_draws(rng) if self.moves == "single" else self._draws(rng)
       self.draw_seconds += time.perf_counter() - t0
-      sample = np.float64(self.state.propose(draws, self.max_angle_shift))
-      self.energy_log.append(float(sample))
-      with np.errstate(over="ignore", invalid="ignore"):        # numpy's comparison: a NaN or inf energy rejects
-        ok = bool(rng.uniform(0.0, 1.0) < np.exp(-(sample - current) / kT))
-      self.accepted.append(ok)
-      if ok:
-        current = sample
-        self.accepted_moves += 1
-        self.acceptance_ratio = self.acceptance_ratio * 0.95 + 0.05
-        self.state.accept()
+      if self.moves == "single":
+        flags, running = self.state.sweep(draws, self.max_angle_shift)
+        self.energy_log.append(running)
+        for ok in flags:        # the recursion once per move, in move order
+          self.accepted.append(ok)
+          self.accepted_moves += int(ok)
+          self.acceptance_ratio = self.acceptance_ratio * 0.95 + (0.05 if ok else 0.0)
       else:
-        self.acceptance_ratio = self.acceptance_ratio * 0.95
+        sample = np.float64(self.state.propose(draws, self.max_angle_shift))
+        self.energy_log.append(float(sample))
+        with np.errstate(over="ignore", invalid="ignore"):        # numpy's comparison: a NaN or inf energy rejects
+          ok = bool(rng.uniform(0.0, 1.0) < np.exp(-(sample - current) / kT))
+        self.accepted.append(ok)
+        if ok:
+          current = sample
+          self.accepted_moves += 1
+          self.acceptance_ratio = self.acceptance_ratio * 0.95 + 0.05
+          self.state.accept()
+        else:
+          self.acceptance_ratio = self.acceptance_ratio * 0.95
       # step size: +-2 % during the first half of the negative steps
       if step < 0 and step < read.initial_step // 2:
         self.max_translation = self.max_translation * (1.02 if self.acceptance_ratio > 0.5 else 0.98)
@@ -304,13 +422,16 @@ class MCMCSampler(object):
       if (step % read.n_save) == 0 and step >= 0:
         if self.verbose:
           print("MCMC, step = ", step, ", wallclock time = ", time.time() - start, ", acceptance ratio = ",
-                self.accepted_moves / (step + 1.0 - read.initial_step))
+                self.accepted_moves / ((step + 1.0 - read.initial_step) * (max(self.n_free, 1) if self.moves == "single" else 1)))
         self._save(step)
     if ((step + 1) % read.n_save) == 0 and step >= 0:         # the "final" save of the reference
       self._save(step + 1)
     self.last_step = step
     if self.verbose:
-      print("\nacceptance ratio = ", self.accepted_moves / (step + 2.0 - read.initial_step))
+      if self.moves == "single":
+        print("\n" + self.info_lines(step)[0])
+      else:
+        print("\nacceptance ratio = ", self.accepted_moves / (step + 2.0 - read.initial_step))
       print("accepted_moves = ", self.accepted_moves)
       print("Total time = ", time.time() - start)
     if self.write_files:
@@ -327,8 +448,10 @@ def main(argv=None):
   ap.add_argument("--device", type=int, default=0)
   ap.add_argument("--potential", choices=("soft", "yukawa"), default="soft")
   ap.add_argument("--rng", choices=("reference", "batched"), default="reference")
+  ap.add_argument("--moves", choices=("all", "single"), default="all",
+                  help="all: every free body in one proposal (the reference); single: a step is one sweep of single-body moves")
   args = ap.parse_args(argv)
-  sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True)
+  sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True, moves=args.moves)
   try:
     sampler.run()
   finally:

@@ -6,6 +6,8 @@ every call) behind the same calls and keyword names:
                       repulsion_strength=.., weight=.., blob_radius=..) -> float
   bodies_potential_hip(bodies, **kwargs) -> 0.0          (the reference's default body potentials are empty)
   compute_total_energy_hip(bodies, r_vectors, **kwargs)  -> U_blobs + U_bodies
+and, beyond the reference, the energy difference of ONE moved body in O(n_body N) (the single-body moves of mcmc.py):
+  body_energy_difference_hip(r_vectors, first, body_new, **kwargs) -> (dU_one_blob, dU_pair)
 `potential="soft"|"yukawa"` is the one extra keyword: the module's own form, or the Yukawa form of the reference's only
 MCMC example (examples/boomerang_suspension/potential_pycuda_user_defined.py).  A reference checkout binds it with
   import rigidmultiblobswall_amd.potential as p; many_body_potential_pycuda.compute_total_energy = p.compute_total_energy_hip
@@ -56,6 +58,27 @@ def blobs_potential_hip(r_vectors, *args, **kwargs):
   ctx.set_positions(r_vectors, kwargs.get('blob_radius'), L, wall=False)
   u_one, u_pair = potential_terms(ctx, **kwargs)
   return u_one + u_pair
+
+
+def body_energy_difference_hip(r_vectors, first, body_new, *args, **kwargs):
+  """(U_one(r') - U_one(r), U_pair(r') - U_pair(r)) for r' = r_vectors with the rows first ... first + len(body_new) - 1
+  replaced by body_new: the touched terms only, each subtracted before it is accumulated (rmb_mcmc_body_delta_device).
+  r_vectors / body_new: numpy arrays or CUDA float64 tensors; same keyword arguments as blobs_potential_hip."""
+  import torch
+  if kwargs.get('potential', 'soft') not in POTENTIAL_FORMS:
+    raise ValueError("potential must be 'soft' or 'yukawa'")
+  ctx = _context()
+  dev = torch.device("cuda", ctx.device)
+  t = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64))).to(dev).reshape(-1, 3).contiguous()  # noqa: E731
+  r, new = t(r_vectors), t(body_new)
+  with torch.cuda.device(dev):
+    out = ctx.mcmc_body_delta_device(r, int(first), new.shape[0], new, kwargs.get('periodic_length'), kwargs.get('repulsion_strength'),
+                                     kwargs.get('debye_length'), kwargs.get('blob_radius'),
+                                     repulsion_strength_wall=kwargs.get('repulsion_strength_wall') or 0.0,
+                                     debye_length_wall=kwargs.get('debye_length_wall') or 1.0, weight=kwargs.get('weight') or 0.0,
+                                     potential=kwargs.get('potential', 'soft'))
+    d = out.cpu().numpy()
+  return float(d[0]), float(d[1])
 
 
 def bodies_potential_hip(bodies, *args, **kwargs):

@@ -7,6 +7,7 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py                  this tree
   python tools/kernel_resources.py OTHER_TREE       OTHER_TREE | this tree, side by side, differing rows marked
   python tools/kernel_resources.py --potential      potential_kernel next to sym_force_kernel, every pair loop of each
+  python tools/kernel_resources.py --moves          body_delta_kernel / move_finish_kernel (rmb_mcmc_moves.hip), every pair loop
   python tools/kernel_resources.py --rigid [TREE]   the dense per-body blocks and the finishing launches of the rigid-body
                                                     operator / Lanczos step (rmb_rigid.hip), every boundary instance
 """
@@ -84,9 +85,14 @@ def pair_loops(asm, mangled, floor=30):
   return out
 
 
-def potential_table(root):
-  """potential_kernel (rmb_potential.hip) next to sym_force_kernel (rmb_sym.hip): resources and every pair loop."""
-  for unit, pattern in (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel")):
+POTENTIAL_KERNELS = (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel"))
+MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
+
+
+def potential_table(root, kernels=POTENTIAL_KERNELS):
+  """potential_kernel (rmb_potential.hip) next to sym_force_kernel (rmb_sym.hip), or the kernels of the single-body moves:
+  resources and every pair loop."""
+  for unit, pattern in kernels:
     asm = subprocess.run([isa_stats.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-S",
                           "--cuda-device-only", "-o", "-", os.path.join(root, "rigidmultiblobswall_amd", "csrc", unit)],
                          check=True, capture_output=True, text=True).stdout
@@ -103,6 +109,9 @@ def potential_table(root):
 if __name__ == "__main__":
   if "--potential" in sys.argv:
     potential_table(isa_stats.ROOT)
+    sys.exit(0)
+  if "--moves" in sys.argv:
+    potential_table(isa_stats.ROOT, MOVE_KERNELS)
     sys.exit(0)
   if "--rigid" in sys.argv:
     root = sys.argv[sys.argv.index("--rigid") + 1] if len(sys.argv) > sys.argv.index("--rigid") + 1 else isa_stats.ROOT
