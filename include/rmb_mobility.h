@@ -412,6 +412,17 @@ int rmb_blob_blob_force_device(rmb_ctx* ctx, double repulsion_strength, double d
  * others are not affected.  debye_length <= 0 or a null pointer: RMB_ERR_ARG. */
 int rmb_body_body_force(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_host);
 int rmb_body_body_force_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_dev);
+/* The energy whose gradient rmb_body_body_force is: out = U_body = sum_{i<j} eps exp(-r_ij/b) / r_ij over the resident points,
+ * which the caller sets to the body LOCATIONS exactly as for rmb_body_body_force (rmb_set_positions with wall = 0; wall = 1 or
+ * a target sub-range: RMB_ERR_STATE), r_ij in the minimal image of every direction with a positive period, z included.  One
+ * more instance of rmb_blob_potential's sweep: the "yukawa" pair expression, but imaged in all three directions, with no wall
+ * gate and no one-blob term (a centre with z <= 0 counts in full, no 1e5 (1 - z)), always fp64.  Each unordered pair once, one
+ * partial per wave, the same finishing launch: no atomics, bit-reproducible for a given configuration, permutation and option
+ * set.  "force_sort", "force_cull" (tile pairs beyond 750 b: exact zeros) and "potential_resort" apply as to
+ * rmb_blob_potential.  One point gives 0; coincident points give +inf.  debye_length <= 0 or a null pointer: RMB_ERR_ARG.
+ * The *_device variant writes the one double to device memory, asynchronously on the context's stream. */
+int rmb_body_body_potential(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_host);
+int rmb_body_body_potential_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:
@@ -455,6 +466,18 @@ int rmb_mcmc_body_delta_device(rmb_ctx* ctx, long n_blobs, const double* r_dev, 
                                const double* periodic_length, double repulsion_strength, double debye_length,
                                double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
                                double* out_dev);
+/* The same with the body-body energy of rmb_body_body_potential (strength body_repulsion_strength, range body_debye_length
+ * > 0) between the n_bodies locations loc_dev (n_bodies x 3): body `body` moves from loc_dev[body] to loc_new_dev[0..2], and
+ *   out_dev = {dU_one, dU_pair, U_body(loc') - U_body(loc)}
+ * where the third entry is the sum over the other bodies j of u(|loc_j - loc'_body|) - u(|loc_j - loc_body|), each subtracted
+ * before it is accumulated, in the minimal image of all three directions (periodic_length[2] is read by this term alone).  The
+ * lane with global index j < n_bodies carries that term; the launch covers max(n_blobs, n_bodies) lanes and every wave stores
+ * a third partial.  One body gives exactly 0.  RMB_ERR_ARG also for a body index outside [0, n_bodies). */
+int rmb_mcmc_body_delta_bb_device(rmb_ctx* ctx, long n_blobs, const double* r_dev, long first, long count, const double* r_body_new_dev,
+                                  long n_bodies, const double* loc_dev, long body, const double* loc_new_dev,
+                                  const double* periodic_length, double repulsion_strength, double debye_length,
+                                  double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
+                                  double body_repulsion_strength, double body_debye_length, double* out_dev);
 /* One sweep of single-body moves over bodies 0 ... n_free - 1 in index order, inside the library.  Body k owns the blobs
  * [body_first[k], body_first[k + 1]) (host table of n_bodies + 1 entries from 0 to n_blobs, non-decreasing: anything else is
  * RMB_ERR_ARG).  Per body two launches: the first composes the proposal from draws_dev[k, 0:3] (displacement) and
@@ -472,6 +495,17 @@ int rmb_mcmc_sweep_device(rmb_ctx* ctx, long n_bodies, long n_free, long n_blobs
                           double max_angle_shift, const double* periodic_length, double repulsion_strength, double debye_length,
                           double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
                           double kT, double* energy_dev, int* accepted_dev);
+/* The same sweep with the body-body energy between the locations loc_dev: the difference launch adds the centre term of
+ * rmb_mcmc_body_delta_bb_device from loc_dev as the earlier moves of the sweep left it (the moved body's new centre is the
+ * proposal it composes), the finishing launch decides on dU_one + dU_pair + dU_body and commits energy_dev = {U_one, U_pair,
+ * U_body} (three doubles; the caller initialises the third e.g. with rmb_body_body_potential_device).  Bodies from n_free on
+ * are never moved but take part in the centre pairs.  A deck without blobs (n_blobs = 0) may pass null blob arrays. */
+int rmb_mcmc_sweep_bb_device(rmb_ctx* ctx, long n_bodies, long n_free, long n_blobs, const long* body_first, const int* blob_ref_dev,
+                             const double* ref_dev, double* loc_dev, double* quat_dev, double* r_dev, const double* draws_dev,
+                             double max_angle_shift, const double* periodic_length, double repulsion_strength, double debye_length,
+                             double repulsion_strength_wall, double debye_length_wall, double weight, double blob_radius, int form,
+                             double body_repulsion_strength, double body_debye_length, double kT, double* energy_dev,
+                             int* accepted_dev);
 /* One-blob forces of the rigid-multiblob driver (multi_bodies/multi_bodies_functions.py:153-188, `blob_external_force`):
  * f = (0, 0, -weight + wall repulsion), wall repulsion = (eps_wall / debye_wall) exp(-(h - a) / debye_wall) above contact
  * (h > a), eps_wall / debye_wall below; r_dev: n x 3 raw coordinates (the caller's, not the resident ones); accumulate != 0

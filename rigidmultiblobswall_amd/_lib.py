@@ -74,6 +74,8 @@ SYMBOLS = {
     "rmb_blob_blob_force_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_body_body_force": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_body_body_force_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_body_body_potential": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_body_body_potential_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_blob_potential": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_blob_potential_device": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_mcmc_propose_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -82,6 +84,11 @@ SYMBOLS = {
                                    [ctypes.c_int, _vp]),
     "rmb_mcmc_sweep_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double,
                                             _vp] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_double, _vp, _vp]),
+    "rmb_mcmc_body_delta_bb_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long,
+                                                    _vp, _vp] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_mcmc_sweep_bb_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double,
+                                               _vp] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                                               _vp, _vp]),
     "rmb_potential_oneshot": (ctypes.c_int, [ctypes.c_long, _vp, _vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_one_blob_force_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                 ctypes.c_int, _vp]),

@@ -516,6 +516,38 @@ class MobilityContext(object):
                                                     ctypes.c_void_p(out.data_ptr())))
     return out
 
+  def body_body_potential(self, repulsion_strength, debye_length):
+    """U_body = sum_{i<j} eps exp(-r_ij/b) / r_ij of the resident points, which the caller has set to the body locations
+    (set_positions(..., wall=False)): the energy whose gradient body_body_force is, minimal image in every periodic
+    direction (z included), no wall gate, always fp64 (rmb_body_body_potential)."""
+    out = np.empty(1)
+    _lib.check(self._lib.rmb_body_body_potential(self._h, float(repulsion_strength), float(debye_length), _ptr(out)))
+    return float(out[0])
+
+  def body_body_potential_device(self, repulsion_strength, debye_length, out=None, device=None):
+    """The same as a CUDA float64 tensor of one entry, asynchronous on the context's stream
+    (rmb_body_body_potential_device).  A caller's out= goes straight to the kernel."""
+    import torch
+    if out is None:
+      out = torch.empty(1, dtype=torch.float64, device=device or ("cuda:%d" % self.device))
+    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 1:
+      raise ValueError("out must be a contiguous CUDA float64 tensor with 1 entry")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_body_body_potential_device(self._h, float(repulsion_strength), float(debye_length),
+                                                        ctypes.c_void_p(out.data_ptr())))
+    return out
+
+  @staticmethod
+  def _body_law(body_potential):
+    """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""
+    try:
+      eps, b = (float(x) for x in body_potential)
+    except (TypeError, ValueError):
+      raise ValueError("body_potential must be (repulsion_strength, debye_length), got %r" % (body_potential,))
+    if not b > 0.0:
+      raise ValueError("body_potential: debye_length must be positive, got %r" % (b,))
+    return eps, b
+
   def _potential_args(self, repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential):
     if potential not in POTENTIAL_FORMS:
       raise ValueError("potential must be one of %s, got %r" % (sorted(POTENTIAL_FORMS), potential))
@@ -569,11 +601,16 @@ class MobilityContext(object):
                                                  float(max_angle_shift), p(loc_new), p(quat_new), p(r_new)))
 
   def mcmc_body_delta_device(self, r, first, count, body_new, periodic_length, repulsion_strength, debye_length, blob_radius,
-                             repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0, potential="soft", out=None):
+                             repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0, potential="soft", out=None,
+                             body_potential=None, locations=None, body=None, location_new=None):
     """{U_one(r') - U_one(r), U_pair(r') - U_pair(r)} as a CUDA float64 tensor of two entries, r' = r (n x 3 CUDA tensor, the
     caller's coordinates -- the resident configuration is not involved) with the rows [first, first + count) replaced by
-    body_new (count x 3): rmb_mcmc_body_delta_device, asynchronous on the context's stream."""
+    body_new (count x 3): rmb_mcmc_body_delta_device, asynchronous on the context's stream.
+    body_potential=(eps, b) with locations= (n_bodies x 3 CUDA tensor), body= (index of the moved body) and location_new=
+    (3 entries, CUDA): three entries, the third the difference of the body-body energy of the locations
+    (rmb_mcmc_body_delta_bb_device)."""
     import torch
+    n_out = 2 if body_potential is None else 3
     args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
     for name, t in (("r", r), ("body_new", body_new)):
       if not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() % 3:
@@ -582,23 +619,39 @@ class MobilityContext(object):
     if not (0 <= first and 0 < count and first + count <= n) or body_new.numel() != 3 * count:
       raise ValueError("the body's blob range [first, first + count) must lie inside r and body_new must have count rows")
     if out is None:
-      out = torch.empty(2, dtype=torch.float64, device=r.device)
-    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2:
-      raise ValueError("out must be a contiguous CUDA float64 tensor with 2 entries")
+      out = torch.empty(n_out, dtype=torch.float64, device=r.device)
+    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != n_out:
+      raise ValueError("out must be a contiguous CUDA float64 tensor with %d entries" % n_out)
     L = _as_f64(np.zeros(3) if periodic_length is None else periodic_length, 3)
     self._follow_torch_stream()
+    if body_potential is not None:
+      body_eps, body_b = self._body_law(body_potential)
+      for name, t in (("locations", locations), ("location_new", location_new)):
+        if not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() % 3 or t.numel() == 0:
+          raise ValueError("%s must be a contiguous CUDA float64 tensor of (rows, 3)" % name)
+      nb = locations.numel() // 3
+      if body is None or not 0 <= int(body) < nb or location_new.numel() != 3:
+        raise ValueError("body must index a row of locations and location_new must have 3 entries")
+      _lib.check(self._lib.rmb_mcmc_body_delta_bb_device(self._h, n, ctypes.c_void_p(r.data_ptr()), first, count, ctypes.c_void_p(body_new.data_ptr()),
+                                                         nb, ctypes.c_void_p(locations.data_ptr()), int(body),
+                                                         ctypes.c_void_p(location_new.data_ptr()), _ptr(L), *args, body_eps, body_b,
+                                                         ctypes.c_void_p(out.data_ptr())))
+      return out
     _lib.check(self._lib.rmb_mcmc_body_delta_device(self._h, n, ctypes.c_void_p(r.data_ptr()), first, count, ctypes.c_void_p(body_new.data_ptr()),
                                                     _ptr(L), *args, ctypes.c_void_p(out.data_ptr())))
     return out
 
   def mcmc_sweep_device(self, body_first, blob_ref, ref, loc, quat, r, draws, n_free, max_angle_shift, periodic_length, kT, energy, accepted,
                         repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0,
-                        potential="soft"):
+                        potential="soft", body_potential=None):
     """One sweep of single-body Metropolis moves over bodies 0 ... n_free - 1, decided and committed on the device
     (rmb_mcmc_sweep_device): loc, quat, r (current blob coordinates) and energy = {U_one, U_pair} (running) are updated in
     place, accepted[k] (int32) is the flag of move k; draws is (n_free, 7).  body_first: host table of n_bodies + 1 blob
-    offsets.  Asynchronous on the context's stream: read the flags and the energy afterwards."""
+    offsets.  Asynchronous on the context's stream: read the flags and the energy afterwards.
+    body_potential=(eps, b): the body-body energy of the locations `loc` takes part (rmb_mcmc_sweep_bb_device) and energy is
+    {U_one, U_pair, U_body}, three entries."""
     import torch
+    n_energy = 2 if body_potential is None else 3
     args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
     body_first = np.ascontiguousarray(body_first, dtype=np.int64).reshape(-1)
     nb, n_blobs, n_free = loc.numel() // 3, r.numel() // 3, int(n_free)
@@ -612,7 +665,7 @@ class MobilityContext(object):
       if not _is_torch_cuda(t) or t.dtype != torch.float64 or not t.is_contiguous():
         raise ValueError("%s must be a contiguous CUDA float64 tensor" % name)
     sizes = (("blob_ref", blob_ref, n_blobs, False), ("loc", loc, 3 * nb, False), ("quat", quat, 4 * nb, False), ("r", r, 3 * n_blobs, False),
-             ("draws", draws, 7 * n_free, True), ("energy", energy, 2, False), ("accepted", accepted, n_free, True))
+             ("draws", draws, 7 * n_free, True), ("energy", energy, n_energy, False), ("accepted", accepted, n_free, True))
     for name, t, size, at_least in sizes:
       if t.numel() < size or (not at_least and t.numel() != size):
         raise ValueError("%s must have %d entries, has %d" % (name, size, t.numel()))
@@ -621,6 +674,11 @@ class MobilityContext(object):
     L = _as_f64(np.zeros(3) if periodic_length is None else periodic_length, 3)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     self._follow_torch_stream()
+    if body_potential is not None:
+      body_eps, body_b = self._body_law(body_potential)
+      _lib.check(self._lib.rmb_mcmc_sweep_bb_device(self._h, nb, n_free, n_blobs, _ptr(body_first), p(blob_ref), p(ref), p(loc), p(quat), p(r), p(draws),
+                                                    float(max_angle_shift), _ptr(L), *args, body_eps, body_b, float(kT), p(energy), p(accepted)))
+      return
     _lib.check(self._lib.rmb_mcmc_sweep_device(self._h, nb, n_free, n_blobs, _ptr(body_first), p(blob_ref), p(ref), p(loc), p(quat), p(r), p(draws),
                                                float(max_angle_shift), _ptr(L), *args, float(kT), p(energy), p(accepted)))
 

@@ -18,6 +18,14 @@
 // stores the two differences (the stateless entry) or decides u < exp(-dE/kT) with numpy's comparison (NaN rejects, -inf
 // accepts) and commits in place: the body's rows of r, its location and quaternion, the running {U_one, U_pair}, the flag.
 // A rejected move writes the flag and nothing else.
+//
+// BODY: E gains U_body = sum_{i<j} eps_b exp(-|x_i - x_j|/b_b) / |x_i - x_j| over the body LOCATIONS (potential_kernel's BODY
+// instance: minimal image in all three directions, no wall gate).  Moving body k touches its n_bodies - 1 centre pairs: the
+// lane whose global index j is a body other than k reads loc[j] (committed in place by the earlier moves of the sweep) and
+// adds u(|loc_j - x'_k|) - u(|loc_j - x_k|) to a third running sum; x'_k is the pose every lane composes (COMPOSE) or the
+// caller's triple.  One more partial per wave through the same butterfly, three sums in the finishing launch, a running
+// energy of three doubles.  Bodies from n_free on are never moved but take part in the pairs.  The grid covers
+// max(n_blobs, n_bodies) lanes.
 #pragma once
 #include "potential_kernels.h"
 
@@ -39,14 +47,18 @@ struct MoveArgs {
   const double* draws;      // (n_free, 7): displacement, rotation vector / max_angle_shift, uniform
   double max_angle_shift;
   double* prop;             // [3 count] proposed coordinates, then [3] location, [4] quaternion (COMPOSE: written by workgroup 0)
-  double* partial;          // [n_waves][2]
+  // BODY: the centre term
+  long n_bodies;
+  const double* loc_new3;   // [3] proposed location of the moved body (!COMPOSE)
+  double body_eps, body_inv_b;
+  double* partial;          // [n_waves][2], BODY: [n_waves][3]
   long n_partial;
   // finishing launch
-  double* out;              // {dU_one, dU_pair} (decide == 0)
+  double* out;              // {dU_one, dU_pair} (decide == 0); BODY: {dU_one, dU_pair, dU_body}
   int decide;
   double kT;
   double *r_rw, *loc_rw, *quat_rw;   // committed in place on acceptance
-  double* energy;           // running {U_one, U_pair}
+  double* energy;           // running {U_one, U_pair}; BODY: {U_one, U_pair, U_body}
   int* accepted;            // [n_free] flag of every move of the sweep
 };
 
@@ -87,7 +99,18 @@ __device__ __forceinline__ double one_blob_full(const PotentialArgs& p, double z
   return z > 0.0 ? one_blob_potential<FORM>(p, z) : 1e5 * (1.0 - z);
 }
 
-template <int FORM, bool PERIODIC, bool COMPOSE>
+// u of one pair of body centres from their separation: the yukawa pair expression on the body law's parameters, imaged in
+// every direction with a positive period
+template <bool PERIODIC>
+__device__ __forceinline__ double centre_potential(const MoveArgs& a, double dx, double dy, double dz) {
+  dx = image<PERIODIC>(a.p.Lx, a.p.iLx, dx); dy = image<PERIODIC>(a.p.Ly, a.p.iLy, dy); dz = image<PERIODIC>(a.p.Lz, a.p.iLz, dz);
+  const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
+  const double ir = r2 > 0.0 ? rsqrt_f64(r2) : __builtin_inf();
+  const double r = r2 > 0.0 ? r2 * ir : 0.0;
+  return a.body_eps * exp_nonpositive(a.p.ec, -r * a.body_inv_b) * ir;
+}
+
+template <int FORM, bool PERIODIC, bool COMPOSE, bool BODY = false>
 __global__ __launch_bounds__(kMoveChunk) void body_delta_kernel(const MoveArgs a) {
   __shared__ double s_old[kMoveChunk][3];
   __shared__ double s_new[kMoveChunk][3];
@@ -114,6 +137,17 @@ __global__ __launch_bounds__(kMoveChunk) void body_delta_kernel(const MoveArgs a
     xn = xo; yn = yo; zn = zo;
   }
   double d_one = 0.0, d_pair = 0.0;
+  [[maybe_unused]] double d_body = 0.0;
+  if constexpr (BODY) {
+    if (j < a.n_bodies && j != a.body) {      // this lane's centre against the moved one, before and after
+      const double lx = a.loc[3 * j], ly = a.loc[3 * j + 1], lz = a.loc[3 * j + 2];
+      const double ox = a.loc[3 * a.body], oy = a.loc[3 * a.body + 1], oz = a.loc[3 * a.body + 2];
+      double nx, ny, nz;
+      if constexpr (COMPOSE) { nx = m.x; ny = m.y; nz = m.z; }
+      else { nx = a.loc_new3[0]; ny = a.loc_new3[1]; nz = a.loc_new3[2]; }
+      d_body = centre_potential<PERIODIC>(a, lx - nx, ly - ny, lz - nz) - centre_potential<PERIODIC>(a, lx - ox, ly - oy, lz - oz);
+    }
+  }
   // the lane's own height gates the pairs in which it is the lower index: j below the body, and j inside it (which meets
   // the body blobs ABOVE it, so that its own chunk is the first it needs)
   const bool own_gate = j_low || in_body;
@@ -159,43 +193,63 @@ __global__ __launch_bounds__(kMoveChunk) void body_delta_kernel(const MoveArgs a
     }
     __syncthreads();      // the next chunk rewrites the slabs
   }
-  // fixed butterfly over the lanes, one pair of partials per wave
+  // fixed butterfly over the lanes, one pair (BODY: triple) of partials per wave
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     d_one += __shfl_xor(d_one, off);
     d_pair += __shfl_xor(d_pair, off);
+    if constexpr (BODY) d_body += __shfl_xor(d_body, off);
   }
   if (lane == 0) {
     const long w = (long)blockIdx.x * kMoveWaves + (t >> 6);
-    a.partial[2 * w] = d_one; a.partial[2 * w + 1] = d_pair;
+    if constexpr (BODY) { a.partial[3 * w] = d_one; a.partial[3 * w + 1] = d_pair; a.partial[3 * w + 2] = d_body; }
+    else { a.partial[2 * w] = d_one; a.partial[2 * w + 1] = d_pair; }
   }
 }
 
 // One workgroup: the partials in a fixed order (thread t: t, t + 256, ...; then a tree over the 256 threads, as
-// potential_finish_kernel), then the result (decide == 0) or the Metropolis decision and the commit.
-static __global__ __launch_bounds__(256) void move_finish_kernel(const MoveArgs a) {
-  __shared__ double s[2][256];
+// potential_finish_kernel), then the result (decide == 0) or the Metropolis decision and the commit.  BODY: three sums.
+template <bool BODY = false>
+__global__ __launch_bounds__(256) void move_finish_kernel(const MoveArgs a) {
+  constexpr int NS = BODY ? 3 : 2;
+  __shared__ double s[NS][256];
   __shared__ int s_ok;
   const int t = threadIdx.x;
-  double u0 = 0.0, u1 = 0.0;
-  for (long k = t; k < a.n_partial; k += 256) { u0 += a.partial[2 * k]; u1 += a.partial[2 * k + 1]; }
-  s[0][t] = u0; s[1][t] = u1;
+  double u[NS];
+#pragma unroll
+  for (int q = 0; q < NS; ++q) u[q] = 0.0;
+  for (long k = t; k < a.n_partial; k += 256) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) u[q] += a.partial[NS * k + q];
+  }
+#pragma unroll
+  for (int q = 0; q < NS; ++q) s[q][t] = u[q];
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) { s[0][t] += s[0][t + off]; s[1][t] += s[1][t + off]; }
+    if (t < off) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) s[q][t] += s[q][t + off];
+    }
     __syncthreads();
   }
   if (!a.decide) {
-    if (t == 0) { a.out[0] = s[0][0]; a.out[1] = s[1][0]; }
+    if (t == 0) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) a.out[q] = s[q][0];
+    }
     return;
   }
   if (t == 0) {
     // numpy's  u < exp(-dE/kT): a NaN compares false (reject), dE = -inf gives exp(inf) = inf (accept)
-    const double dE = s[0][0] + s[1][0];
-    const double u = a.draws[7 * a.body + 6];
-    const int ok = u < exp(-dE / a.kT) ? 1 : 0;
+    double dE = s[0][0] + s[1][0];
+    if constexpr (BODY) dE += s[2][0];
+    const double u01 = a.draws[7 * a.body + 6];
+    const int ok = u01 < exp(-dE / a.kT) ? 1 : 0;
     a.accepted[a.body] = ok;
-    if (ok) { a.energy[0] += s[0][0]; a.energy[1] += s[1][0]; }
+    if (ok) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) a.energy[q] += s[q][0];
+    }
     s_ok = ok;
   }
   __syncthreads();

@@ -15,6 +15,11 @@
 //     the caller's order, counts iff z_i > 0.  Record .w carries the caller's index (perm[s] of the Morton-sorted copy).
 //     Units whose two tiles lie above the wall (zmin > 0, wave-uniform from the tile bounds) skip the test.
 //   * minimal image in x and y only; distinct blobs at r = 0 give the finite contact value (soft) / inf (yukawa).
+//
+// BODY: the same sweep over body LOCATIONS, U_body = sum_{i<j} eps exp(-r_ij/b) / r_ij -- the energy whose gradient is
+// BodyYukawaLaw (sym_force_kernels.h).  The yukawa pair expression with three differences: the minimal image in every direction
+// with a positive period, z included (the image rule of the force law); no wall gate and no one-blob term (a centre with
+// z <= 0 counts in full); one result.  Tile culling by 750 b with the z period in the tile gap.
 #pragma once
 #include "pair_ops.h"
 #include "sym_schedule.h"
@@ -39,7 +44,10 @@ struct PotentialArgs {
   ExpConsts ec;
   double* partial;      // [n_waves][2] = (one-blob, pair) sums of every wave of the launch
   long n_partial;       // n_waves
-  double* out;          // {U_one_blob, U_pair}
+  double* out;          // {U_one_blob, U_pair}; BODY: {U_body}
+  // BODY only (kept behind the fields every instance reads, whose offsets the blob forms' register allocation depends on)
+  double Lz, iLz;       // the blob forms ignore periodic_length[2]
+  int n_out;            // 2, BODY: 1
 };
 
 // exp of any argument from exp_nonpositive: 1 / exp(-x) for x > 0 (one more rounding; inf where exp overflows).  The
@@ -93,8 +101,16 @@ __device__ __forceinline__ double image(double L, double iL, double d) {
   return d;
 }
 
-template <int FORM, bool PERIODIC>
+// separation in z: the blob forms take it as it is, the body centres take its minimal image
+template <bool PERIODIC, bool BODY>
+__device__ __forceinline__ double image_z(const PotentialArgs& a, double d) {
+  if constexpr (BODY) return image<PERIODIC>(a.Lz, a.iLz, d);
+  return d;
+}
+
+template <int FORM, bool PERIODIC, bool BODY = false>
 __global__ __launch_bounds__(64 * kSymWaves) void potential_kernel(const PotentialArgs a) {
+  static_assert(!BODY || FORM == POT_YUKAWA, "the body-body law is the yukawa pair expression");
   __shared__ double4 rec_all[kSymWaves][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -121,7 +137,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void potential_kernel(const Potenti
       const bool diag = (I == J);
       // diagonal unit: step 0 = the one-blob terms, steps 1..32 = every unordered pair of the tile once
       // (lane l meets l + k; at k = 32 both lanes of a pair would meet: the lower half takes it), 33..63 empty
-      const bool idle = diag ? (k0 > 32) : (tile_gap2(a.bounds, I, J, PERIODIC ? a.Lx : 0.0, PERIODIC ? a.Ly : 0.0, 0.0) > a.cull2);
+      const bool idle = diag ? (k0 > 32) : (tile_gap2(a.bounds, I, J, PERIODIC ? a.Lx : 0.0, PERIODIC ? a.Ly : 0.0, PERIODIC && BODY ? a.Lz : 0.0) > a.cull2);
       if (idle) {   // beyond the reach of the exponential: every term of the unit is exactly zero
         if (k1 == 64) unit_next(a.order, a.n_tiles, I, J);
         continue;
@@ -144,7 +160,9 @@ __global__ __launch_bounds__(64 * kSymWaves) void potential_kernel(const Potenti
         rec[lane] = p;
       } else {
         rec[lane] = make_double4(vi_ok ? xi : -1e100, vi_ok ? yi : -1e100, vi_ok ? zi : -1e100, idx_i);
-        if (k0 == 0 && vi_ok) u_one += (zi > 0.0) ? one_blob_potential<FORM>(a, zi) : 1e5 * (1.0 - zi);
+        if constexpr (!BODY) {
+          if (k0 == 0 && vi_ok) u_one += (zi > 0.0) ? one_blob_potential<FORM>(a, zi) : 1e5 * (1.0 - zi);
+        }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -152,24 +170,25 @@ __global__ __launch_bounds__(64 * kSymWaves) void potential_kernel(const Potenti
       const int kb = (diag && k0 < 1) ? 1 : k0;
       const int ke = (diag && k1 > 33) ? 33 : k1;
       // a tile that reaches the wall plane (zmin <= 0) needs the lower-index test of the reference's loop limits
-      const bool above = a.bounds[6L * I + 2] > 0.0 && a.bounds[6L * J + 2] > 0.0;
+      // (BODY: no gate at all -- padding sits 2e100 away, where the exponential is exactly 0)
+      const bool above = BODY || (a.bounds[6L * I + 2] > 0.0 && a.bounds[6L * J + 2] > 0.0);
       // step 32 of a diagonal unit is met from both of its lanes: it is peeled off the loop and taken by the lower half
       const bool peel = diag && kb <= 32 && ke > 32;
       const int kl = peel ? 32 : ke;
       if (above) {
         for (int k = kb; k < kl; ++k) {
           const double4 q = rec[(lane + k) & 63];
-          u_pair += pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), zi - q.z);
+          u_pair += pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), image_z<PERIODIC, BODY>(a, zi - q.z));
         }
         if (peel) {
           const double4 q = rec[(lane + 32) & 63];
-          const double u = pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), zi - q.z);
+          const double u = pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), image_z<PERIODIC, BODY>(a, zi - q.z));
           u_pair += lane < 32 ? u : 0.0;
         }
       } else {
         for (int k = kb; k < ke; ++k) {
           const double4 q = rec[(lane + k) & 63];
-          const double u = pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), zi - q.z);
+          const double u = pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, xi - q.x), image<PERIODIC>(a.Ly, a.iLy, yi - q.y), image_z<PERIODIC, BODY>(a, zi - q.z));
           const double z_low = idx_i < q.w ? zi : q.z;       // the blob with the lower caller's index decides
           const bool real = idx_i < 1e17 && q.w < 1e17;      // padding carries index 1e18
           const bool skip = (peel && k == 32 && lane >= 32) || !real || !(z_low > 0.0);
@@ -200,7 +219,10 @@ static __global__ __launch_bounds__(256) void potential_finish_kernel(const Pote
     if ((int)threadIdx.x < off) { s[0][threadIdx.x] += s[0][threadIdx.x + off]; s[1][threadIdx.x] += s[1][threadIdx.x + off]; }
     __syncthreads();
   }
-  if (threadIdx.x == 0) { a.out[0] = s[0][0]; a.out[1] = s[1][0]; }
+  if (threadIdx.x == 0) {
+    if (a.n_out == 1) a.out[0] = s[1][0];      // BODY: the one-blob sums are zeros
+    else { a.out[0] = s[0][0]; a.out[1] = s[1][0]; }
+  }
 }
 
 }  // namespace rmb

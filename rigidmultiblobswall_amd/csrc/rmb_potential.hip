@@ -11,27 +11,33 @@ namespace rmbi {
 namespace {
 
 // The sweep + the finishing launch on the context's stream; the two sums end up in out_dev[0..1].
+// `body`: the resident points are body locations and the energy is the body-body Yukawa law's (the BODY instance of
+// potential_kernels.h): the yukawa pair expression without contact distance, wall gate and one-blob term, imaged in all three
+// directions; ONE sum in out_dev[0].
 int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
-                          double* out_dev) {
+                          double* out_dev, bool body = false) {
   if (int rc = check_ready(c)) return rc;
   if (!out_dev) return fail(RMB_ERR_ARG, "null output pointer");
   if (form != rmb::POT_SOFT && form != rmb::POT_YUKAWA) return fail(RMB_ERR_ARG, "potential form must be 0 (soft) or 1 (yukawa)");
   if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
   if (eps_wall != 0.0 && !(b_wall > 0.0)) return fail(RMB_ERR_ARG, "debye_length_wall must be positive when repulsion_strength_wall is not zero");
-  if (c->wall) return fail(RMB_ERR_STATE, "the potential uses raw heights: call rmb_set_positions with wall = 0");
+  if (c->wall) return fail(RMB_ERR_STATE, body ? "the body-body potential uses raw locations: call rmb_set_positions with wall = 0"
+                                               : "the potential uses raw heights: call rmb_set_positions with wall = 0");
   if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the potential is a sum over all blobs: reset the target range");
   RMB_HIP(hipSetDevice(c->device));
   const long n = c->n, tiles = (n + 63) / 64;
-  if (n == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, 2 * sizeof(double), c->stream)); return 0; }
+  if (n == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, (body ? 1 : 2) * sizeof(double), c->stream)); return 0; }
   if (n > 0xffffffffL) return fail(RMB_ERR_ARG, "potential: more than 2^32 blobs");
 
   typedef rmb::PotentialArgs A;
   A a;
-  // x and y only: the struct has no z period, the reference ignores periodic_length[2]
+  // x and y only (fill_sym_args): the reference ignores periodic_length[2]
   fill_sym_args(a, SymConf{(const double4*)c->pos.p, n, {c->L[0], c->L[1], c->L[2]}, 0, nullptr}, c, 0.0, tiles * (tiles + 1) / 2, 0, 1);
+  a.Lz = body ? c->L[2] : 0.0; a.iLz = inv_length(a.Lz);      // the body centres alone see the z period
+  a.n_out = body ? 1 : 2;
   a.perm = nullptr;
   a.order = 0; a.xcd = 0;      // as the force sweep (rmb_sym.hip): after culling the surviving units hug the diagonal
-  const bool periodic = a.Lx > 0 || a.Ly > 0;
+  const bool periodic = a.Lx > 0 || a.Ly > 0 || a.Lz > 0;
   a.eps = eps; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
   a.eps_wall = eps_wall; a.inv_b_wall = eps_wall != 0.0 ? 1.0 / b_wall : 0.0; a.a = blob_radius; a.weight = weight;
   a.ec = exp_consts();
@@ -52,7 +58,9 @@ int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, dou
   const double reach = form == rmb::POT_SOFT ? 2.0 * blob_radius + 750.0 * b : 750.0 * b;
   a.cull2 = c->opt_force_cull ? reach * reach : std::numeric_limits<double>::infinity();
 
-  const SymKernel k = form == rmb::POT_SOFT
+  const SymKernel k = body ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true, true>>(0)
+                                       : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false, true>>(0))
+                      : form == rmb::POT_SOFT
                           ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, true>>(0) : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, false>>(0))
                           : (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true>>(0)
                                       : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false>>(0));
@@ -130,6 +138,21 @@ int rmb_blob_potential(rmb_ctx* c, double eps, double b, double eps_wall, double
   if (int rc = c->out.reserve(2 * sizeof(double))) return rc;
   if (int rc = rmbi::potential_device_impl(c, eps, b, eps_wall, b_wall, weight, blob_radius, form, (double*)c->out.p)) return rc;
   RMB_HIP(hipMemcpyAsync(out, c->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  RMB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int rmb_body_body_potential_device(rmb_ctx* c, double eps, double b, double* out_dev) {
+  return rmbi::potential_device_impl(c, eps, b, 0.0, 1.0, 0.0, 0.0, rmb::POT_YUKAWA, out_dev, true);
+}
+
+int rmb_body_body_potential(rmb_ctx* c, double eps, double b, double* out) {
+  if (int rc = rmbi::check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  if (int rc = c->out.reserve(sizeof(double))) return rc;
+  if (int rc = rmb_body_body_potential_device(c, eps, b, (double*)c->out.p)) return rc;
+  RMB_HIP(hipMemcpyAsync(out, c->out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   RMB_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -1,7 +1,7 @@
 """Metropolis sampler of rigid-body configurations -- many_bodyMCMC/many_body_MCMC.py on MI355X.
 
     python -m rigidmultiblobswall_amd.mcmc [inputfile] [--device N] [--potential soft|yukawa] [--rng reference|batched]
-                                           [--moves all|single]
+                                           [--moves all|single] [--body-potential none|deck|EPS,B]
 
 Same decks, same outputs (.inputfile, .random_state, .clones per saved step or one appended .config, .time, .MCMC_info)
 and, with rng="reference", the same chain as the reference script for the same seed: the draws come from a
@@ -22,6 +22,14 @@ rmb_mcmc_sweep_device then runs two launches per body -- proposal + energy diffe
 commit in place -- without a host synchronisation in between, and the host reads the flags and the running energy.  The
 acceptance recursion is applied once per flag, the +-2 % rule once per step; at every save the full energy is recomputed
 (energy_drift) and the running value reset to it.
+
+`body_potential=(eps, b)` (beyond the reference, whose body potentials are empty): the energy gains the Yukawa repulsion
+between body locations, U_body = sum_{i<j} eps exp(-r_ij/b) / r_ij in the minimal image of every periodic direction -- the
+energy of the steppers' body-body forces, so that the chain samples what a Brownian deck with
+`body_body_force_torque_implementation python|hip` relaxes to; "deck" takes the two numbers the steppers would take from
+this deck.  The locations are the resident points of a second context: moves="all" adds rmb_body_body_potential of the
+proposed locations to every proposal's energy, moves="single" runs rmb_mcmc_sweep_bb_device with a running energy of three
+doubles.  None (the default) is the reference's sampler: the deck option is ignored.
 
 `MCMCSampler(..., energy=f)` runs the same chain with f(r_vectors) -> float as the energy and numpy state instead (the
 host tests replay the reference's fixtures with the numpy restatement that way); without it the energy is the HIP one --
@@ -76,6 +84,42 @@ def rotation_matrices(quat):
   return 2.0 * R
 
 
+def body_body_energy(loc, periodic_length, repulsion_strength, debye_length):
+  """numpy twin of rmb_body_body_potential: sum_{i<j} eps exp(-r/b) / r between the rows of loc, minimal image in every
+  direction with a positive period (project_to_periodic_image: the image count is truncated after adding half away from
+  zero)."""
+  x = np.asarray(loc, dtype=np.float64).reshape(-1, 3)
+  i, j = np.triu_indices(len(x), 1)
+  d = x[j] - x[i]
+  for k in range(3):
+    Lk = float(periodic_length[k])
+    if Lk > 0:
+      d[:, k] -= np.trunc(d[:, k] / Lk + 0.5 * np.sign(d[:, k])) * Lk
+  r = np.sqrt(np.sum(d * d, axis=1))
+  with np.errstate(divide="ignore", invalid="ignore"):
+    return float(np.sum(repulsion_strength * np.exp(-r / debye_length) / r))
+
+
+def resolve_body_potential(body_potential, read):
+  """None, or (eps, b) as two floats: a tuple as given, "deck" = the law the steppers apply to this deck."""
+  if body_potential is None:
+    return None
+  if isinstance(body_potential, str):
+    if body_potential != "deck":
+      raise ValueError("body_potential must be None, 'deck' or (repulsion_strength, debye_length), got %r" % (body_potential,))
+    if read.body_body_force_torque_implementation not in ("python", "hip"):
+      raise ValueError("body_potential='deck': the deck does not switch body-body forces on "
+                       "(body_body_force_torque_implementation %s; python or hip)" % (read.body_body_force_torque_implementation,))
+    body_potential = (read.repulsion_strength, read.debye_length)
+  try:
+    eps, b = (float(x) for x in body_potential)
+  except (TypeError, ValueError):
+    raise ValueError("body_potential must be None, 'deck' or (repulsion_strength, debye_length), got %r" % (body_potential,))
+  if not b > 0.0:
+    raise ValueError("body_potential: debye_length must be positive, got %r" % (b,))
+  return eps, b
+
+
 def compose_proposal(loc, quat, draws, n_free, max_angle_shift):
   """numpy twin of rmb_mcmc_propose_device's first half: (loc_new, quat_new)."""
   loc_new, quat_new = loc.copy(), quat.copy()
@@ -105,12 +149,20 @@ class _HostState(object):
     R = rotation_matrices(quat)
     return np.einsum("bij,bj->bi", R[s.blob_body], s.ref_all[s.blob_ref]) + loc[s.blob_body]
 
+  def _total(self, loc, quat):
+    """The caller's energy of the blob coordinates, plus the body-body term of the locations when it is on."""
+    e = self.energy_fn(self._blobs(loc, quat))
+    law = self.s.body_potential
+    if law is not None:
+      e = e + body_body_energy(loc, self.s.periodic_length, law[0], law[1])
+    return e
+
   def current_energy(self):
-    return self.energy_fn(self._blobs(self.loc, self.quat))
+    return self._total(self.loc, self.quat)
 
   def propose(self, draws, max_angle_shift):
     self.loc_new, self.quat_new = compose_proposal(self.loc, self.quat, draws, self.s.n_free, max_angle_shift)
-    return self.energy_fn(self._blobs(self.loc_new, self.quat_new))
+    return self._total(self.loc_new, self.quat_new)
 
   def accept(self):
     self.loc, self.quat = self.loc_new, self.quat_new
@@ -126,7 +178,7 @@ class _HostState(object):
       loc_k, quat_k = compose_proposal(self.loc[k:k + 1], self.quat[k:k + 1], draws[k:k + 1, 0:6], 1, max_angle_shift)
       loc_new, quat_new = self.loc.copy(), self.quat.copy()
       loc_new[k], quat_new[k] = loc_k[0], quat_k[0]
-      sample = np.float64(self.energy_fn(self._blobs(loc_new, quat_new)))
+      sample = np.float64(self._total(loc_new, quat_new))
       with np.errstate(over="ignore", invalid="ignore"):
         bound = np.exp(-(sample - self.running) / kT)
         ok = bool(draws[k, 6] < bound)
@@ -152,7 +204,8 @@ class _HostState(object):
 
 
 class _DeviceState(object):
-  """Bodies as CUDA tensors; proposal and energy are HIP launches on one context."""
+  """Bodies as CUDA tensors; proposal and energy are HIP launches on one context.  With a body potential a second context
+  on the same device holds the body locations as its resident points (the blob view stays where it is)."""
 
   def __init__(self, sampler, device):
     import torch
@@ -160,6 +213,9 @@ class _DeviceState(object):
     self.torch, self.s = torch, sampler
     self.dev = torch.device("cuda", int(device))
     self.ctx = MobilityContext(int(device))
+    self.law = sampler.body_potential
+    self.body_ctx = MobilityContext(int(device)) if self.law is not None else None
+    self.u_body = torch.zeros(1, dtype=torch.float64, device=self.dev)
     t = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt).to(self.dev)   # noqa: E731
     self.loc, self.quat = t(sampler.loc0), t(sampler.quat0)
     self.loc_new, self.quat_new = torch.empty_like(self.loc), torch.empty_like(self.quat)
@@ -173,7 +229,8 @@ class _DeviceState(object):
       self.body_first = np.ascontiguousarray(sampler.body_first, dtype=np.int64)
       self.draws7_host = torch.zeros((max(sampler.n_free, 1), 7), dtype=torch.float64).pin_memory()
       self.draws7 = torch.zeros((max(sampler.n_free, 1), 7), dtype=torch.float64, device=self.dev)
-      self.energy = torch.zeros(2, dtype=torch.float64, device=self.dev)        # running {U_one, U_pair}
+      # running {U_one, U_pair}, with a body potential {U_one, U_pair, U_body}
+      self.energy = torch.zeros(2 if self.law is None else 3, dtype=torch.float64, device=self.dev)
       self.flags = torch.zeros(max(sampler.n_free, 1), dtype=torch.int32, device=self.dev)
 
   def _energy_terms(self, out=None):
@@ -184,11 +241,20 @@ class _DeviceState(object):
                                             repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
                                             weight=s.weight, potential=s.potential, out=out)
 
+  def _body_energy(self, loc, out):
+    """U_body of the locations `loc` into out (one entry): the energy sweep on the second context."""
+    s = self.s
+    with self.torch.cuda.device(self.dev):
+      self.body_ctx.set_positions(loc, s.blob_radius, s.periodic_length, wall=False)
+      return self.body_ctx.body_body_potential_device(self.law[0], self.law[1], out=out)
+
   def recompute_energy(self):
-    """The full energy of the current coordinates (the energy sweep); the running pair on the device becomes it.
+    """The full energy of the current coordinates (the energy sweeps); the running sums on the device become it.
     -> (running before, full)"""
     before = float(self.energy.sum().item())
-    self._energy_terms(out=self.energy)
+    self._energy_terms(out=self.energy[:2])
+    if self.law is not None:
+      self._body_energy(self.loc, self.energy[2:])
     return before, float(self.energy.sum().item())
 
   def sweep(self, draws, max_angle_shift):
@@ -202,7 +268,7 @@ class _DeviceState(object):
       self.ctx.mcmc_sweep_device(self.body_first, self.blob_ref, self.ref, self.loc, self.quat, self.r_new, self.draws7, s.n_free,
                                  max_angle_shift, s.periodic_length, s.kT, self.energy, self.flags, s.repulsion_strength, s.debye_length,
                                  s.blob_radius, repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
-                                 weight=s.weight, potential=s.potential)
+                                 weight=s.weight, potential=s.potential, body_potential=self.law)
     flags = self.flags[:s.n_free].cpu().numpy()
     return [bool(f) for f in flags], float(self.energy.sum().item())
 
@@ -213,6 +279,8 @@ class _DeviceState(object):
       u_one, u_pair = self.ctx.blob_potential(s.repulsion_strength, s.debye_length, s.blob_radius,
                                               repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
                                               weight=s.weight, potential=s.potential)
+    if self.law is not None:      # of the proposed locations (current_energy proposes the current ones)
+      return u_one + u_pair + float(self._body_energy(self.loc_new, self.u_body).item())
     return u_one + u_pair
 
   def _propose(self, loc, quat, n_free, max_angle_shift):
@@ -247,6 +315,8 @@ class _DeviceState(object):
 
   def close(self):
     self.ctx.close()
+    if self.body_ctx is not None:
+      self.body_ctx.close()
 
 
 class MCMCSampler(object):
@@ -258,7 +328,7 @@ class MCMCSampler(object):
   (running energy, recomputed full energy) of every save."""
 
   def __init__(self, read, device=0, potential="soft", rng="reference", energy=None, write_files=True, verbose=False,
-               check_user_potential=True, keep_saved=None, moves="all"):
+               check_user_potential=True, keep_saved=None, moves="all", body_potential=None):
     if check_user_potential:
       refuse_user_defined_potential(".")
     if potential not in ("soft", "yukawa"):
@@ -281,6 +351,8 @@ class MCMCSampler(object):
     self.weight = 1.0 * read.g
     self.kT = read.kT
     self.repulsion_strength, self.debye_length = read.repulsion_strength, read.debye_length
+    # None: the reference's sampler (the deck's body-body option is ignored); (eps, b): the Yukawa energy between locations
+    self.body_potential = resolve_body_potential(body_potential, read)
     self.repulsion_strength_wall, self.debye_length_wall = read.repulsion_strength_wall, read.debye_length_wall
     # bodies, structure after structure (many_body_MCMC.py:107-125)
     refs, locs, quats, blob_body, blob_ref = [], [], [], [], []
@@ -369,6 +441,12 @@ class MCMCSampler(object):
       offset += self.body_types[i]
 
   def info_lines(self, last_step):
+    lines = self._info_lines(last_step)
+    if self.body_potential is not None:
+      lines.append("body_potential = yukawa repulsion_strength %s debye_length %s" % self.body_potential)
+    return lines
+
+  def _info_lines(self, last_step):
     if self.moves == "single":      # per move
       return ["acceptance ratio = " + str(self.accepted_moves / max(1.0, float(len(self.accepted)))),
               "accepted_moves = " + str(self.accepted_moves),
@@ -450,8 +528,18 @@ def main(argv=None):
   ap.add_argument("--rng", choices=("reference", "batched"), default="reference")
   ap.add_argument("--moves", choices=("all", "single"), default="all",
                   help="all: every free body in one proposal (the reference); single: a step is one sweep of single-body moves")
+  ap.add_argument("--body-potential", default="none", metavar="none|deck|EPS,B",
+                  help="Yukawa repulsion between body locations: none (the reference), deck (the steppers' law for this deck: "
+                       "repulsion_strength, debye_length; needs body_body_force_torque_implementation python|hip) or two numbers")
   args = ap.parse_args(argv)
-  sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True, moves=args.moves)
+  body_potential = None if args.body_potential == "none" else args.body_potential
+  if body_potential not in (None, "deck"):
+    try:
+      body_potential = tuple(float(x) for x in body_potential.split(","))
+    except ValueError:
+      ap.error("--body-potential takes none, deck or EPS,B (two numbers), got %r" % (args.body_potential,))
+  sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True, moves=args.moves,
+                        body_potential=body_potential)
   try:
     sampler.run()
   finally:

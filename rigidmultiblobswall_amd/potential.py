@@ -4,7 +4,9 @@ Replaces many_bodyMCMC/many_body_potential_pycuda.py:234-351 (one CUDA thread pe
 every call) behind the same calls and keyword names:
   blobs_potential_hip(r_vectors, periodic_length=L, debye_length_wall=.., repulsion_strength_wall=.., debye_length=..,
                       repulsion_strength=.., weight=.., blob_radius=..) -> float
-  bodies_potential_hip(bodies, **kwargs) -> 0.0          (the reference's default body potentials are empty)
+  bodies_potential_hip(bodies, **kwargs) -> 0.0          (the reference's default body potentials are empty); with
+                      body_potential=(eps, b) the Yukawa energy between the body locations (the law of forces.py's
+                      body-body forces), HIP
   compute_total_energy_hip(bodies, r_vectors, **kwargs)  -> U_blobs + U_bodies
 and, beyond the reference, the energy difference of ONE moved body in O(n_body N) (the single-body moves of mcmc.py):
   body_energy_difference_hip(r_vectors, first, body_new, **kwargs) -> (dU_one_blob, dU_pair)
@@ -82,8 +84,22 @@ def body_energy_difference_hip(r_vectors, first, body_new, *args, **kwargs):
 
 
 def bodies_potential_hip(bodies, *args, **kwargs):
-  """one_body_potential / body_body_potential of the reference are empty (many_body_potential_pycuda.py:125-155)."""
-  return 0.0
+  """one_body_potential / body_body_potential of the reference are empty (many_body_potential_pycuda.py:125-155): 0.0.
+  body_potential=(eps, b): U_body = sum_{i<j} eps exp(-r_ij/b) / r_ij between the locations of `bodies` (objects with a
+  .location, or an (n, 3) array), minimal image in every direction of periodic_length= with a positive period
+  (rmb_body_body_potential) -- the energy of the steppers' body-body forces."""
+  law = kwargs.get('body_potential')
+  if law is None:
+    return 0.0
+  eps, b = MobilityContext._body_law(law)
+  if hasattr(bodies, "__len__") and len(bodies) and hasattr(bodies[0], "location"):
+    loc = np.array([np.asarray(body.location, dtype=np.float64) for body in bodies]).reshape(-1, 3)
+  else:
+    loc = np.asarray(bodies, dtype=np.float64).reshape(-1, 3)
+  L = kwargs.get('periodic_length')
+  ctx = _context()
+  ctx.set_positions(loc, kwargs.get('blob_radius') or 1.0, np.zeros(3) if L is None else L, wall=False)
+  return ctx.body_body_potential(eps, b)
 
 
 def compute_total_energy_hip(bodies, r_vectors, *args, **kwargs):
