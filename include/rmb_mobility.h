@@ -423,6 +423,28 @@ int rmb_body_body_force_device(rmb_ctx* ctx, double repulsion_strength, double d
  * The *_device variant writes the one double to device memory, asynchronously on the context's stream. */
 int rmb_body_body_potential(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_host);
 int rmb_body_body_potential_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_dev);
+/* Histogram of the pair distances of the resident points: the counts behind the radial distribution function g(r)
+ * (multi_bodies/examples/Radial_Dist_Test/gr_pseudo2D_single_blob.cpp).  Uses the raw positions as rmb_blob_potential
+ * (rmb_set_positions with wall = 0; wall = 1 or a target sub-range: RMB_ERR_STATE).  For every unordered pair i < j:
+ * r = |x_i - x_j| in the minimal image of every direction with a positive period (z included; the reference program's
+ * formula, valid for separations of any number of periods), in fp64; if r < r_max, hist[(int)(r / dr)] += 1 with
+ * dr = r_max / n_bins.  Coincident points count in bin 0.  One count per UNORDERED pair (the reference program counts 2).
+ * The potential's sweep (each pair once, "force_sort" from 2048 points on, "force_cull": tile pairs further apart than r_max
+ * are skipped, which drops no pair with r < r_max) with uint32 counters in LDS and integer atomics to the uint64 bins:
+ * the counts are the same bits for every launch plan and option set.  Always fp64, single device.
+ *   rmb_pair_histogram_device  ADDS into hist_dev[n_bins] (the caller zeroes it and may accumulate frames), asynchronous
+ *                              on the context's stream;
+ *   rmb_pair_histogram         zeroes hist_host[n_bins] first; synchronous.
+ * rmb_pair_histogram_frames_device: the same counts for n_frames frames of n points each, frames_dev = (n_frames, n, 3)
+ * packed doubles on the device, L = 3 periods on the host (<= 0: open), in ONE launch over (frame, tile pair), no sort, no
+ * culling; adds into hist_dev.  It neither reads nor writes the resident configuration or any other state of the
+ * context (only its device and stream), so a sampler may call it between energy evaluations.
+ * RMB_ERR_ARG: a null pointer, r_max <= 0, n_bins < 1 or n_bins > 8192.  n = 0, n = 1 and n_frames = 0 leave the histogram
+ * unchanged. */
+int rmb_pair_histogram_device(rmb_ctx* ctx, double r_max, long n_bins, unsigned long long* hist_dev);
+int rmb_pair_histogram(rmb_ctx* ctx, double r_max, long n_bins, unsigned long long* hist_host);
+int rmb_pair_histogram_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, double r_max,
+                                     long n_bins, unsigned long long* hist_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

@@ -537,6 +537,48 @@ class MobilityContext(object):
                                                         ctypes.c_void_p(out.data_ptr())))
     return out
 
+  def pair_histogram(self, r_max, n_bins):
+    """Counts of the unordered pairs i < j of the resident points (set_positions(..., wall=False)) per distance bin:
+    r < r_max lands in bin int(r / (r_max / n_bins)), r in the minimal image of every periodic direction (z included), fp64
+    (rmb_pair_histogram).  numpy uint64 array of n_bins entries: the counts behind g(r) (correlation.RadialDistribution)."""
+    out = np.zeros(int(n_bins), dtype=np.uint64)
+    _lib.check(self._lib.rmb_pair_histogram(self._h, float(r_max), int(n_bins), _ptr(out) if out.size else None))
+    return out
+
+  def _hist_out(self, n_bins, out, device):
+    """The out= rules of the histogram entries: a contiguous CUDA int64 tensor of n_bins entries, which is ADDED to (zeros
+    when it is made here)."""
+    import torch
+    if out is None:
+      return torch.zeros(max(int(n_bins), 0), dtype=torch.int64, device=device or ("cuda:%d" % self.device))
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == int(n_bins)):
+      raise ValueError("out must be a contiguous CUDA int64 tensor with n_bins entries")
+    return out
+
+  def pair_histogram_device(self, r_max, n_bins, out=None, device=None):
+    """The same counts ADDED to a CUDA int64 tensor of n_bins entries (out=None: a new tensor of zeros), asynchronous on the
+    context's stream (rmb_pair_histogram_device): call it once per frame to accumulate.  A caller's out= goes straight to
+    the kernel."""
+    out = self._hist_out(n_bins, out, device)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_pair_histogram_device(self._h, float(r_max), int(n_bins), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
+
+  def pair_histogram_frames_device(self, frames, periodic_length, r_max, n_bins, out=None):
+    """The counts of every frame of `frames` -- a contiguous CUDA float64 tensor (n_frames, n, 3), or (n, 3) for one frame --
+    ADDED to a CUDA int64 tensor of n_bins entries in one launch (rmb_pair_histogram_frames_device).  periodic_length:
+    three periods (<= 0: open).  The resident configuration is neither read nor changed."""
+    if not _is_torch_cuda(frames) or not frames.is_contiguous() or frames.dim() not in (2, 3) or frames.shape[-1] != 3:
+      raise ValueError("frames must be a contiguous CUDA float64 tensor of shape (n_frames, n, 3) or (n, 3)")
+    n_frames, n = (1, frames.shape[0]) if frames.dim() == 2 else (frames.shape[0], frames.shape[1])
+    L = _as_f64(periodic_length, 3)
+    out = self._hist_out(n_bins, out, frames.device)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_pair_histogram_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, int(n_frames),
+                                                          int(n), _ptr(L), float(r_max), int(n_bins),
+                                                          ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
+
   @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""

@@ -24,6 +24,8 @@
 //                    atomic-free) and the Metropolis proposal of the equilibrium sampler
 //   rmb_mcmc_moves.hip  single-body Metropolis moves (mcmc_move_kernels.h): energy difference of one moved body, and a
 //                    whole sweep of moves decided and committed on the device
+//   rmb_pair_hist.hip  histogram of pair distances (pair_hist_kernels.h: the potential's schedule and culling, integer counters
+//                    in LDS, integer atomics to the caller's uint64 bins): resident points, and a batch of caller-owned frames
 //   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
 //                    points and the two fused device sweeps of the concentration solve
 #pragma once

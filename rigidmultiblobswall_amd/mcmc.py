@@ -1,7 +1,7 @@
 """Metropolis sampler of rigid-body configurations -- many_bodyMCMC/many_body_MCMC.py on MI355X.
 
     python -m rigidmultiblobswall_amd.mcmc [inputfile] [--device N] [--potential soft|yukawa] [--rng reference|batched]
-                                           [--moves all|single] [--body-potential none|deck|EPS,B]
+                                           [--moves all|single] [--body-potential none|deck|EPS,B] [--gr RMAX,BINS]
 
 Same decks, same outputs (.inputfile, .random_state, .clones per saved step or one appended .config, .time, .MCMC_info)
 and, with rng="reference", the same chain as the reference script for the same seed: the draws come from a
@@ -30,6 +30,13 @@ energy of the steppers' body-body forces, so that the chain samples what a Brown
 this deck.  The locations are the resident points of a second context: moves="all" adds rmb_body_body_potential of the
 proposed locations to every proposal's energy, moves="single" runs rmb_mcmc_sweep_bb_device with a running energy of three
 doubles.  None (the default) is the reference's sampler: the deck option is ignored.
+
+`gr=(r_max, n_bins)` (beyond the reference, which post-processes its `.config` with gr_pseudo2D_single_blob.cpp): at every
+saved step the body locations, already on the device, go through the batch entry of the HIP pair-distance histogram
+(rmb_pair_histogram_frames_device, one frame; the resident configuration of the energy sweeps is not touched), and at the end
+`<output_name>.gr.dat` holds `r g hist` in that program's format (correlation.py; normalisation "3d" when all three periods are
+positive, else "pseudo2d").  With an energy= function the locations are uploaded for it.  Off by default; off, nothing the
+sampler does or writes changes.
 
 `MCMCSampler(..., energy=f)` runs the same chain with f(r_vectors) -> float as the energy and numpy state instead (the
 host tests replay the reference's fixtures with the numpy restatement that way); without it the energy is the HIP one --
@@ -143,6 +150,7 @@ class _HostState(object):
     self.s, self.energy_fn = sampler, energy
     self.loc, self.quat = sampler.loc0.copy(), sampler.quat0.copy()
     self.running, self.decision_margin = None, np.inf      # moves="single"
+    self.gr_ctx = None      # context of the g(r) hook, made on first use
 
   def _blobs(self, loc, quat):
     s = self.s
@@ -199,8 +207,20 @@ class _HostState(object):
   def configuration(self):
     return self.loc, self.quat
 
+  def gr_add(self, r_max, n_bins, hist):
+    """The pair histogram of the current locations added to hist (CUDA int64 tensor): an upload, then the batch entry."""
+    import torch
+    if self.gr_ctx is None:
+      from .context import MobilityContext
+      self.gr_ctx = MobilityContext(hist.device.index)
+    with torch.cuda.device(hist.device):
+      frame = torch.from_numpy(np.ascontiguousarray(self.loc, dtype=np.float64).reshape(1, -1, 3)).to(hist.device)
+      self.gr_ctx.pair_histogram_frames_device(frame, self.s.periodic_length, r_max, n_bins, out=hist)
+
   def close(self):
-    pass
+    if self.gr_ctx is not None:
+      self.gr_ctx.close()
+      self.gr_ctx = None
 
 
 class _DeviceState(object):
@@ -313,6 +333,12 @@ class _DeviceState(object):
   def configuration(self):
     return self.loc.cpu().numpy(), self.quat.cpu().numpy()
 
+  def gr_add(self, r_max, n_bins, hist):
+    """The pair histogram of the current locations added to hist (CUDA int64 tensor): the batch entry on the locations where
+    they are; neither context's resident configuration is involved."""
+    with self.torch.cuda.device(self.dev):
+      self.ctx.pair_histogram_frames_device(self.loc.view(1, -1, 3), self.s.periodic_length, r_max, n_bins, out=hist)
+
   def close(self):
     self.ctx.close()
     if self.body_ctx is not None:
@@ -328,7 +354,7 @@ class MCMCSampler(object):
   (running energy, recomputed full energy) of every save."""
 
   def __init__(self, read, device=0, potential="soft", rng="reference", energy=None, write_files=True, verbose=False,
-               check_user_potential=True, keep_saved=None, moves="all", body_potential=None):
+               check_user_potential=True, keep_saved=None, moves="all", body_potential=None, gr=None):
     if check_user_potential:
       refuse_user_defined_potential(".")
     if potential not in ("soft", "yukawa"):
@@ -340,6 +366,18 @@ class MCMCSampler(object):
     if moves == "single" and energy is None and not isinstance(device, (int, np.integer)):
       raise ValueError("moves='single' takes a device index, not %r" % (device,))
     self.moves = moves
+    self.gr = None
+    if gr is not None:
+      try:
+        r_max, n_bins = gr
+        self.gr = (float(r_max), int(n_bins))
+      except (TypeError, ValueError):
+        raise ValueError("gr must be None or (r_max, n_bins), got %r" % (gr,))
+      if not self.gr[0] > 0.0 or not 1 <= self.gr[1] <= 8192 or self.gr[1] != n_bins:
+        raise ValueError("gr: r_max must be positive and n_bins an integer 1 ... 8192, got %r" % (gr,))
+      if not isinstance(device, (int, np.integer)):
+        raise ValueError("gr takes a device index, not %r" % (device,))
+    self.device = device
     self.read = read = ReadInput(read) if isinstance(read, str) else read
     self.potential, self.rng_mode, self.write_files, self.verbose = potential, rng, write_files, verbose
     if read.n_steps <= read.initial_step:
@@ -385,6 +423,11 @@ class MCMCSampler(object):
     # saved configurations stay in memory only when asked for, or when no file receives them
     self.keep_saved = (not write_files) if keep_saved is None else bool(keep_saved)
     self.draw_seconds = 0.0
+    self.gr_frames, self._gr_hist = 0, None
+    if self.gr is not None:      # refuses a box the normalisation cannot serve before anything runs
+      from . import correlation
+      self.gr_normalisation = "3d" if np.all(self.periodic_length > 0) else "pseudo2d"
+      correlation.normalise(np.zeros(1), 1, max(self.n_bodies, 1), self.periodic_length, self.gr[0], self.gr_normalisation)
     self.state = _HostState(self, energy) if energy is not None else _DeviceState(self, device)
 
   def close(self):
@@ -422,6 +465,8 @@ class MCMCSampler(object):
   def _save(self, step):
     if self.moves == "single":      # the running energy against a full evaluation, which it then restarts from
       self.energy_drift[step] = self.state.recompute_energy()
+    if self.gr is not None:
+      self._gr_add()
     loc, quat = self.state.configuration()
     if self.keep_saved:
       self.saved[step] = (np.array(loc), np.array(quat))
@@ -439,6 +484,29 @@ class MCMCSampler(object):
           x, q = loc[offset + j], quat[offset + j]
           f.write("%s %s %s %s %s %s %s\n" % (float(x[0]), float(x[1]), float(x[2]), float(q[0]), float(q[1]), float(q[2]), float(q[3])))
       offset += self.body_types[i]
+
+  # ---- g(r) of the saved configurations ------------------------------------------------------------------------------------
+  def _gr_add(self):
+    if self._gr_hist is None:
+      import torch
+      self._gr_hist = torch.zeros(self.gr[1], dtype=torch.int64, device=torch.device("cuda", int(self.device)))
+    self.state.gr_add(self.gr[0], self.gr[1], self._gr_hist)
+    self.gr_frames += 1
+
+  @property
+  def gr_counts(self):
+    """unordered pairs per bin over the saved configurations so far (numpy uint64); None with gr off"""
+    if self.gr is None:
+      return None
+    return np.zeros(self.gr[1], dtype=np.uint64) if self._gr_hist is None else self._gr_hist.cpu().numpy().astype(np.uint64)
+
+  def gr_text(self):
+    """`r g hist` of the saved configurations in the reference program's format"""
+    from . import correlation
+    counts = self.gr_counts
+    r = (np.arange(self.gr[1]) + 0.5) * (self.gr[0] / self.gr[1])
+    g = correlation.normalise(counts, max(self.gr_frames, 1), self.n_bodies, self.periodic_length, self.gr[0], self.gr_normalisation)
+    return correlation.format_gr(r, g, counts)
 
   def info_lines(self, last_step):
     lines = self._info_lines(last_step)
@@ -517,6 +585,9 @@ class MCMCSampler(object):
         f.write(str(time.time() - start) + "\n")
       with open(read.output_name + ".MCMC_info", "w") as f:
         f.write("\n".join(self.info_lines(step)) + "\n")
+      if self.gr is not None:
+        with open(read.output_name + ".gr.dat", "w") as f:
+          f.write(self.gr_text())
     return self
 
 
@@ -531,7 +602,16 @@ def main(argv=None):
   ap.add_argument("--body-potential", default="none", metavar="none|deck|EPS,B",
                   help="Yukawa repulsion between body locations: none (the reference), deck (the steppers' law for this deck: "
                        "repulsion_strength, debye_length; needs body_body_force_torque_implementation python|hip) or two numbers")
+  ap.add_argument("--gr", default=None, metavar="RMAX,BINS",
+                  help="accumulate the pair-distance histogram of the body locations at every saved step and write <output_name>.gr.dat")
   args = ap.parse_args(argv)
+  gr = None
+  if args.gr is not None:
+    try:
+      r_max, n_bins = args.gr.split(",")
+      gr = (float(r_max), int(n_bins))
+    except ValueError:
+      ap.error("--gr takes RMAX,BINS (a number and an integer), got %r" % (args.gr,))
   body_potential = None if args.body_potential == "none" else args.body_potential
   if body_potential not in (None, "deck"):
     try:
@@ -539,7 +619,7 @@ def main(argv=None):
     except ValueError:
       ap.error("--body-potential takes none, deck or EPS,B (two numbers), got %r" % (args.body_potential,))
   sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True, moves=args.moves,
-                        body_potential=body_potential)
+                        body_potential=body_potential, gr=gr)
   try:
     sampler.run()
   finally:

@@ -8,6 +8,8 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py OTHER_TREE       OTHER_TREE | this tree, side by side, differing rows marked
   python tools/kernel_resources.py --potential      potential_kernel next to sym_force_kernel, every pair loop of each
   python tools/kernel_resources.py --moves          body_delta_kernel / move_finish_kernel (rmb_mcmc_moves.hip), every pair loop
+  python tools/kernel_resources.py --pair-hist      pair_hist_kernel (rmb_pair_hist.hip) next to potential_kernel; `lds` is the static part
+                                                    (the staging slabs), the counters add 4 n_bins bytes of dynamic LDS
   python tools/kernel_resources.py --rigid [TREE]   the dense per-body blocks and the finishing launches of the rigid-body
                                                     operator / Lanczos step (rmb_rigid.hip), every boundary instance
 """
@@ -86,6 +88,7 @@ def pair_loops(asm, mangled, floor=30):
 
 
 POTENTIAL_KERNELS = (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel"))
+PAIR_HIST_KERNELS = (("rmb_pair_hist.hip", "pair_hist_kernel"), ("rmb_potential.hip", "potential_kernel"))
 MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
 
 
@@ -112,6 +115,9 @@ if __name__ == "__main__":
     sys.exit(0)
   if "--moves" in sys.argv:
     potential_table(isa_stats.ROOT, MOVE_KERNELS)
+    sys.exit(0)
+  if "--pair-hist" in sys.argv:
+    potential_table(isa_stats.ROOT, PAIR_HIST_KERNELS)
     sys.exit(0)
   if "--rigid" in sys.argv:
     root = sys.argv[sys.argv.index("--rigid") + 1] if len(sys.argv) > sys.argv.index("--rigid") + 1 else isa_stats.ROOT
