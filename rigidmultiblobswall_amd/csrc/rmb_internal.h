@@ -20,11 +20,11 @@
 //   rmb_krylov.hip   O(N) helpers of the rigid-body solve: batched 2 x 2 block product, fused Gram-Schmidt step
 //   rmb_gmres.hip    the whole right-preconditioned GMRES of the rigid-body problem and the Lanczos forcings as one call each
 //                    (host loop native too); one workspace layout for both (krylov_workspace)
-//   rmb_potential.hip  total potential energy of a blob configuration (potential_kernels.h: symmetric sweep to a scalar,
-//                    atomic-free) and the Metropolis proposal of the equilibrium sampler
+//   rmb_potential.hip  total potential energy of a blob configuration (potential_kernels.h: a policy of the pair-once frame,
+//                    pair_once_kernels.h; atomic-free) and the Metropolis proposal of the equilibrium sampler
 //   rmb_mcmc_moves.hip  single-body Metropolis moves (mcmc_move_kernels.h): energy difference of one moved body, and a
 //                    whole sweep of moves decided and committed on the device
-//   rmb_pair_hist.hip  histogram of pair distances (pair_hist_kernels.h: the potential's schedule and culling, integer counters
+//   rmb_pair_hist.hip  histogram of pair distances (pair_hist_kernels.h: the other policy of that frame, integer counters
 //                    in LDS, integer atomics to the caller's uint64 bins): resident points, and a batch of caller-owned frames
 //   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
 //                    points and the two fused device sweeps of the concentration solve
@@ -285,11 +285,15 @@ SymKernel sym_kernel_of(size_t static_lds, int waves_per_eu = 0) {
   static int occ = 0;
   return SymKernel{(const void*)KERNEL, static_lds, &occ, waves_per_eu, sym_kernel_launch<Args, KERNEL>};
 }
-// The non-pinned plan of the culling sweeps (blob-blob forces, potential energy): "sym_oversub" resident rounds capped
-// by one workgroup per 256 steps, and a quarter of "sym_chunk_steps" per strided chunk -- the surviving units are few
-// and uneven, shorter chunks balance them (3D cloud of 1e5 blobs 3.36 -> 3.05 ms, monolayer unchanged;
-// tools/experiments/exp_force_ab.py).  *chunk_steps = 0: one contiguous range per wave.
-void plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps);
+// The non-pinned plan of the culling sweeps (blob-blob forces, potential energy, pair histogram): `rounds` resident rounds
+// (0: "sym_oversub") capped by one workgroup per 256 steps, and a quarter of "sym_chunk_steps" per strided chunk -- the
+// surviving units are few and uneven, shorter chunks balance them (3D cloud of 1e5 blobs 3.36 -> 3.05 ms, monolayer
+// unchanged; tools/experiments/exp_force_ab.py).  *chunk_steps = 0: one contiguous range per wave.
+// `dyn_lds` > 0: the residency is asked for with that much dynamic LDS (every time: it is the caller's number).
+// `wg_pair_cap` > 0: the workgroups are doubled until the busiest one meets fewer pairs than that (64 per step and wave),
+// and the plan is refused in `who`'s name if that takes more workgroups than one launch has.  Without a cap it cannot fail.
+int plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps, long rounds = 0,
+                    size_t dyn_lds = 0, double wg_pair_cap = 0.0, const char* who = "");
 void shard_ranges(long n, long n_units, long shard, long nshards, long* step_begin, long* step_end, long* self_begin,
                   long* self_end);
 int sym_accumulators(rmb_ctx* c, long n_pad);
@@ -365,16 +369,37 @@ int sym_launch(rmb_ctx* c, const SymKernel& k, int path, long blocks, size_t dyn
   RMB_HIP(hipGetLastError());
   return 0;
 }
-// Tile bounds of the culling sweeps (forces, potential): the Morton-sorted copy (rmb_sort.hip; `keep_perm`: along the
-// permutation that is already there) or the bounds of the caller's order; use_tile_bounds points the arguments at them.
+// Tile bounds of the culling sweeps (forces, potential, pair histogram): the Morton-sorted copy (rmb_sort.hip; `keep_perm`:
+// along the permutation that is already there) or the bounds of the caller's order; use_tile_bounds points the arguments
+// at them (and at the permutation, where the sweep wants the caller's indices).
 int build_tile_bounds(rmb_ctx* c, bool sorted, bool keep_perm);
+template <class A, class = void> struct HasPerm : std::false_type {};
+template <class A> struct HasPerm<A, std::void_t<decltype(A::perm)>> : std::true_type {};
 template <class Args>
 void use_tile_bounds(const rmb_ctx* c, Args& a) {
   if (c->force_sorted) {
     a.pos = (const double4*)c->fpos.p;
-    a.perm = (const unsigned*)c->fperm.p;
+    if constexpr (HasPerm<Args>::value) a.perm = (const unsigned*)c->fperm.p;
   }
   a.bounds = (const double*)c->tile_bounds.p;
+}
+// Resident preparation of the pair-once sweeps (pair_once_kernels.h: potential energy, pair histogram), all of it before
+// the launch plan: the state and size checks in the caller's words, then spatial order and tile bounds (pair_once_resident,
+// rmb_sym.hip), then the arguments the frame reads.  `reuse_perm`: the Morton permutation may be kept by the
+// "potential_resort" rule; else it is rebuilt.  *empty: fewer than `n_min` points -- nothing was prepared, nothing to launch.
+// The caller sets Lz / iLz (who sees the z period differs), cull2 and its own fields.
+struct PairOnceErrors { const char *wall, *range, *size; };
+int pair_once_resident(rmb_ctx* c, const PairOnceErrors& msg, long n_min, bool reuse_perm, bool* empty);
+template <class Args>
+int pair_once_prepare(rmb_ctx* c, Args& a, const PairOnceErrors& msg, long n_min, bool reuse_perm, bool* empty) {
+  if (int rc = pair_once_resident(c, msg, n_min, reuse_perm, empty)) return rc;
+  if (*empty) return 0;
+  const long tiles = (c->n + 63) / 64;
+  fill_sym_args(a, SymConf{(const double4*)c->pos.p, c->n, {c->L[0], c->L[1], c->L[2]}, 0, nullptr}, c, 0.0, tiles * (tiles + 1) / 2, 0, 1);
+  a.order = 0; a.xcd = 0;      // as the force sweep (rmb_sym.hip): after culling the surviving units hug the diagonal
+  if constexpr (HasPerm<Args>::value) a.perm = nullptr;
+  use_tile_bounds(c, a);
+  return 0;
 }
 // no_finalize: leave the raw sums in the accumulators (c->symbuf: [3][n_pad], unscaled, no self term) -- the caller
 // launches its own finishing kernel (rmb_rigid_operator_device); not for the pseudo-periodic / fp32 routes

@@ -20,37 +20,16 @@ int check_hist_args(double r_max, long n_bins, const void* hist) {
 }
 
 template <bool BATCH>
-const void* hist_kernel(bool periodic) {
-  return periodic ? (const void*)rmb::pair_hist_kernel<true, BATCH> : (const void*)rmb::pair_hist_kernel<false, BATCH>;
+SymKernel hist_kernel(bool periodic) {
+  const size_t slabs = sizeof(double4) * 64 * rmb::kSymWaves;
+  return periodic ? sym_kernel_of<A, rmb::pair_hist_kernel<true, BATCH>>(slabs) : sym_kernel_of<A, rmb::pair_hist_kernel<false, BATCH>>(slabs);
 }
 
-// Launch plan: two resident rounds of workgroups (every workgroup ends with up to n_bins global atomics, so fewer and
-// longer workgroups than the energy sweep's eight rounds), at least 256 steps each, a wave's steps cut into strided
-// chunks as in plan_cull_sweep.  A workgroup's LDS counters are uint32: the plan is refined until a workgroup meets
-// fewer than 2^31 pairs (64 per step), and refused if it cannot be.
-int plan_hist(rmb_ctx* c, const void* fn, size_t dyn_lds, long total_steps, long* blocks, long* chunk_steps) {
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * rmb::kSymWaves, dyn_lds) != hipSuccess || occ < 1) occ = 1;
-  if (occ > 8) occ = 8;
-  long b = c->n_cu * occ * 2;
-  const long need = (total_steps + 255) / 256;
-  if (b > need) b = need;
-  if (b < 1) b = 1;
-  for (;;) {
-    const long waves = b * rmb::kSymWaves;
-    const long spw = (total_steps + waves - 1) / waves;
-    const long ch = chunked_steps(c, total_steps, waves, spw, c->opt_sym_chunk_steps / 4);
-    const long step = ch < spw ? ch : spw;
-    const long n_chunks = (total_steps + step - 1) / step;
-    const long per_wave = (n_chunks + waves - 1) / waves * step;      // steps of the busiest wave
-    if ((double)per_wave * rmb::kSymWaves * 64.0 < 2147483648.0) {
-      *blocks = b;
-      *chunk_steps = ch < spw ? ch : 0;
-      return 0;
-    }
-    if (b > (1L << 30)) return fail(RMB_ERR_ARG, "pair histogram: too many pairs for one launch");
-    b *= 2;
-  }
+// Launch plan: plan_cull_sweep with two resident rounds of workgroups (every workgroup ends with up to n_bins global
+// atomics, so fewer and longer workgroups than the energy sweep's eight rounds).  A workgroup's LDS counters are uint32:
+// the plan is refined until a workgroup meets fewer than 2^31 pairs, and refused if it cannot be.
+int plan_hist(rmb_ctx* c, const SymKernel& k, size_t dyn_lds, long total_steps, long* blocks, long* chunk_steps) {
+  return plan_cull_sweep(c, k, total_steps, blocks, chunk_steps, 2, dyn_lds, 2147483648.0, "pair histogram");
 }
 
 void fill_hist(A& a, double r_max, long n_bins, unsigned long long* hist) {
@@ -63,37 +42,23 @@ void fill_hist(A& a, double r_max, long n_bins, unsigned long long* hist) {
 int hist_resident_impl(rmb_ctx* c, double r_max, long n_bins, unsigned long long* hist_dev) {
   if (int rc = check_ready(c)) return rc;
   if (int rc = check_hist_args(r_max, n_bins, hist_dev)) return rc;
-  if (c->wall) return fail(RMB_ERR_STATE, "the pair histogram uses raw positions: call rmb_set_positions with wall = 0");
-  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the pair histogram runs over all points: reset the target range");
-  const long n = c->n, tiles = (n + 63) / 64;
-  if (n < 2) return 0;
-  if (n > 0xffffffffL) return fail(RMB_ERR_ARG, "pair histogram: more than 2^32 points");
-  RMB_HIP(hipSetDevice(c->device));
-
   A a{};
-  fill_sym_args(a, SymConf{(const double4*)c->pos.p, n, {c->L[0], c->L[1], c->L[2]}, 0, nullptr}, c, 0.0, tiles * (tiles + 1) / 2, 0, 1);
+  // spatial order, tile bounds and the frame's arguments, always with a fresh Morton permutation: what is left behind is
+  // what a potential evaluation that rebuilt its permutation leaves
+  const PairOnceErrors msg{"the pair histogram uses raw positions: call rmb_set_positions with wall = 0",
+                           "the pair histogram runs over all points: reset the target range", "pair histogram: more than 2^32 points"};
+  bool empty;
+  if (int rc = pair_once_prepare(c, a, msg, 2, false, &empty)) return rc;
+  if (empty) return 0;
   a.Lz = c->L[2]; a.iLz = inv_length(a.Lz);
-  a.order = 0; a.xcd = 0;      // as the energy sweep: after culling the surviving units hug the diagonal
   const bool periodic = a.Lx > 0 || a.Ly > 0 || a.Lz > 0;
   fill_hist(a, r_max, n_bins, hist_dev);
-
-  // Spatial order and tile bounds as the energy sweep's (rmb_potential.hip), always with a fresh Morton permutation: what
-  // is left behind is what a potential evaluation that rebuilt its permutation leaves.
-  const bool sorted = c->opt_force_sort && tiles >= 32;
-  if (int rc = build_tile_bounds(c, sorted, false)) return rc;
-  if (sorted) c->pot_sort_age = 0;
-  c->tile_bounds_valid = true;
-  c->force_sorted = sorted;
-  a.pos = sorted ? (const double4*)c->fpos.p : (const double4*)c->pos.p;
-  a.bounds = (const double*)c->tile_bounds.p;
   a.cull2 = c->opt_force_cull ? a.r_max2 : std::numeric_limits<double>::infinity();
 
   const size_t dyn = (size_t)n_bins * sizeof(unsigned);
-  SymKernel k = periodic ? sym_kernel_of<A, rmb::pair_hist_kernel<true, false>>(sizeof(double4) * 64 * rmb::kSymWaves)
-                         : sym_kernel_of<A, rmb::pair_hist_kernel<false, false>>(sizeof(double4) * 64 * rmb::kSymWaves);
+  const SymKernel k = hist_kernel<false>(periodic);
   long blocks;
-  if (int rc = plan_hist(c, k.fn, dyn, a.step_end, &blocks, &a.chunk_steps)) return rc;
-  if (blocks > 0x7fffffffL) return fail(RMB_ERR_ARG, "pair histogram: too many pairs for one launch");
+  if (int rc = plan_hist(c, k, dyn, a.step_end, &blocks, &a.chunk_steps)) return rc;
   return sym_launch(c, k, 1, blocks, dyn, a, rmb::PairConsts{}, (void (*)(A)) nullptr, 0);
 }
 
@@ -143,13 +108,12 @@ int rmb_pair_histogram_frames_device(rmb_ctx* c, const double* frames_dev, long 
   rmbi::fill_hist(a, r_max, n_bins, hist_dev);
   const bool periodic = a.Lx > 0 || a.Ly > 0 || a.Lz > 0;
   const size_t dyn = (size_t)n_bins * sizeof(unsigned);
+  const rmbi::SymKernel k = rmbi::hist_kernel<true>(periodic);
   long blocks;
-  if (int rc = rmbi::plan_hist(c, rmbi::hist_kernel<true>(periodic), dyn, a.step_end, &blocks, &a.chunk_steps)) return rc;
-  if (blocks > 0x7fffffffL) return fail(RMB_ERR_ARG, "pair histogram: too many pairs for one launch");
+  if (int rc = rmbi::plan_hist(c, k, dyn, a.step_end, &blocks, &a.chunk_steps)) return rc;
   // launched directly: nothing of the context but its device and stream is read, nothing is written (no bookkeeping of the
   // last launch, no timing slot)
-  if (periodic) hipLaunchKernelGGL((rmb::pair_hist_kernel<true, true>), dim3((unsigned)blocks), dim3(64 * rmb::kSymWaves), dyn, c->stream, a);
-  else hipLaunchKernelGGL((rmb::pair_hist_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * rmb::kSymWaves), dyn, c->stream, a);
+  k.launch(&a, rmb::PairConsts{}, (unsigned)blocks, dyn, c->stream);
   RMB_HIP(hipGetLastError());
   return 0;
 }

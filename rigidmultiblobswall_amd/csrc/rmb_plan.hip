@@ -178,16 +178,33 @@ long chunked_steps(const rmb_ctx* c, long total, long n_sched, long spw, long ta
   return (total + n_sched * rounds - 1) / (n_sched * rounds);
 }
 
-void plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps) {
-  long b = c->n_cu * resident_blocks(k.fn, k.occ) * c->opt_sym_oversub;
+int plan_cull_sweep(rmb_ctx* c, const SymKernel& k, long total_steps, long* blocks, long* chunk_steps, long rounds, size_t dyn_lds,
+                    double wg_pair_cap, const char* who) {
+  int occ = 0;
+  if (dyn_lds == 0) occ = resident_blocks(k.fn, k.occ);
+  else {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, 64 * rmb::kSymWaves, dyn_lds) != hipSuccess || occ < 1) occ = 1;
+    if (occ > 8) occ = 8;
+  }
+  long b = c->n_cu * occ * (rounds > 0 ? rounds : c->opt_sym_oversub);
   const long need = (total_steps + 255) / 256;
   if (b > need) b = need;
   if (b < 1) b = 1;
-  const long waves = b * rmb::kSymWaves;
-  const long spw = (total_steps + waves - 1) / waves;
-  const long ch = chunked_steps(c, total_steps, waves, spw, c->opt_sym_chunk_steps / 4);
-  *blocks = b;
-  *chunk_steps = ch < spw ? ch : 0;
+  for (;; b *= 2) {
+    const long waves = b * rmb::kSymWaves;
+    const long spw = (total_steps + waves - 1) / waves;
+    const long ch = chunked_steps(c, total_steps, waves, spw, c->opt_sym_chunk_steps / 4);
+    *blocks = b;
+    *chunk_steps = ch < spw ? ch : 0;
+    if (!(wg_pair_cap > 0.0)) return 0;
+    const long step = ch < spw ? ch : spw;
+    const long n_chunks = (total_steps + step - 1) / step;
+    const long per_wave = (n_chunks + waves - 1) / waves * step;      // steps of the busiest wave
+    if ((double)per_wave * rmb::kSymWaves * 64.0 < wg_pair_cap) break;
+    if (b > (1L << 30)) return fail(RMB_ERR_ARG, std::string(who) + ": too many pairs for one launch");
+  }
+  if (b > 0x7fffffffL) return fail(RMB_ERR_ARG, std::string(who) + ": too many pairs for one launch");
+  return 0;
 }
 
 // whether the symmetric (each unordered pair once) path applies to the resident configuration

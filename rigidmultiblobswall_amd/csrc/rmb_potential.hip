@@ -21,40 +21,22 @@ int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, dou
   if (form != rmb::POT_SOFT && form != rmb::POT_YUKAWA) return fail(RMB_ERR_ARG, "potential form must be 0 (soft) or 1 (yukawa)");
   if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
   if (eps_wall != 0.0 && !(b_wall > 0.0)) return fail(RMB_ERR_ARG, "debye_length_wall must be positive when repulsion_strength_wall is not zero");
-  if (c->wall) return fail(RMB_ERR_STATE, body ? "the body-body potential uses raw locations: call rmb_set_positions with wall = 0"
-                                               : "the potential uses raw heights: call rmb_set_positions with wall = 0");
-  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the potential is a sum over all blobs: reset the target range");
-  RMB_HIP(hipSetDevice(c->device));
-  const long n = c->n, tiles = (n + 63) / 64;
-  if (n == 0) { RMB_HIP(hipMemsetAsync(out_dev, 0, (body ? 1 : 2) * sizeof(double), c->stream)); return 0; }
-  if (n > 0xffffffffL) return fail(RMB_ERR_ARG, "potential: more than 2^32 blobs");
-
   typedef rmb::PotentialArgs A;
   A a;
-  // x and y only (fill_sym_args): the reference ignores periodic_length[2]
-  fill_sym_args(a, SymConf{(const double4*)c->pos.p, n, {c->L[0], c->L[1], c->L[2]}, 0, nullptr}, c, 0.0, tiles * (tiles + 1) / 2, 0, 1);
-  a.Lz = body ? c->L[2] : 0.0; a.iLz = inv_length(a.Lz);      // the body centres alone see the z period
+  // spatial order, tile bounds and the frame's arguments; the Morton permutation ages by "potential_resort"
+  const PairOnceErrors msg{body ? "the body-body potential uses raw locations: call rmb_set_positions with wall = 0"
+                                : "the potential uses raw heights: call rmb_set_positions with wall = 0",
+                           "the potential is a sum over all blobs: reset the target range", "potential: more than 2^32 blobs"};
+  bool empty;
+  if (int rc = pair_once_prepare(c, a, msg, 1, true, &empty)) return rc;
+  if (empty) { RMB_HIP(hipMemsetAsync(out_dev, 0, (body ? 1 : 2) * sizeof(double), c->stream)); return 0; }
+  // x and y only (fill_sym_args): the reference ignores periodic_length[2]; the body centres alone see the z period
+  a.Lz = body ? c->L[2] : 0.0; a.iLz = inv_length(a.Lz);
   a.n_out = body ? 1 : 2;
-  a.perm = nullptr;
-  a.order = 0; a.xcd = 0;      // as the force sweep (rmb_sym.hip): after culling the surviving units hug the diagonal
   const bool periodic = a.Lx > 0 || a.Ly > 0 || a.Lz > 0;
   a.eps = eps; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
   a.eps_wall = eps_wall; a.inv_b_wall = eps_wall != 0.0 ? 1.0 / b_wall : 0.0; a.a = blob_radius; a.weight = weight;
   a.ec = exp_consts();
-
-  // Spatial order and tile bounds.  The bounds are recomputed for every evaluation (the culling is correct for ANY
-  // order); the Morton permutation is kept and rebuilt on every "potential_resort"-th evaluation.
-  const bool sorted = c->opt_force_sort && tiles >= 32;
-  bool rebuild = true;
-  if (sorted) rebuild = c->fperm_n != n || c->pot_sort_age < 0 || c->pot_sort_age + 1 >= c->opt_potential_resort;
-  if (int rc = build_tile_bounds(c, sorted, !rebuild)) return rc;
-  if (sorted) c->pot_sort_age = rebuild ? 0 : c->pot_sort_age + 1;
-  // What the force path finds (rmb_sym.hip): after a full sort, or bounds in the caller's order, exactly what it would have
-  // built itself for this configuration -- it may use them; a sorted copy along a REUSED permutation is correct too, but
-  // not the order the forces alone would sum in, so the force path is told to build its own.
-  c->tile_bounds_valid = rebuild;
-  c->force_sorted = sorted;
-  use_tile_bounds(c, a);
   const double reach = form == rmb::POT_SOFT ? 2.0 * blob_radius + 750.0 * b : 750.0 * b;
   a.cull2 = c->opt_force_cull ? reach * reach : std::numeric_limits<double>::infinity();
 

@@ -322,6 +322,29 @@ int build_tile_bounds(rmb_ctx* c, bool sorted, bool keep_perm) {
   return 0;
 }
 
+int pair_once_resident(rmb_ctx* c, const PairOnceErrors& msg, long n_min, bool reuse_perm, bool* empty) {
+  if (c->wall) return fail(RMB_ERR_STATE, msg.wall);
+  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, msg.range);
+  const long n = c->n, tiles = (n + 63) / 64;
+  if (n > 0xffffffffL) return fail(RMB_ERR_ARG, msg.size);
+  RMB_HIP(hipSetDevice(c->device));
+  *empty = n < n_min;
+  if (*empty) return 0;
+  // Spatial order and tile bounds.  The bounds are recomputed for every evaluation (the culling is correct for ANY
+  // order); the Morton permutation is rebuilt, or with `reuse_perm` kept and rebuilt on every "potential_resort"-th evaluation.
+  const bool sorted = c->opt_force_sort && tiles >= 32;
+  bool rebuild = true;
+  if (sorted && reuse_perm) rebuild = c->fperm_n != n || c->pot_sort_age < 0 || c->pot_sort_age + 1 >= c->opt_potential_resort;
+  if (int rc = build_tile_bounds(c, sorted, !rebuild)) return rc;
+  if (sorted) c->pot_sort_age = rebuild ? 0 : c->pot_sort_age + 1;
+  // What the force path finds (sym_force_device): after a full sort, or bounds in the caller's order, exactly what it would have
+  // built itself for this configuration -- it may use them; a sorted copy along a REUSED permutation is correct too, but
+  // not the order the forces alone would sum in, so the force path is told to build its own.
+  c->tile_bounds_valid = rebuild;
+  c->force_sorted = sorted;
+  return 0;
+}
+
 // Symmetric pair-force sweep (sym_force_kernels.h: each unordered pair once, F_ji = -F_ij) of pair shard `shard` of
 // `nshards` into a full-length result; atomic flushes.  Tile culling and the fp32 twin as the options say.
 // `law`: the blob-blob contact law, or the body-body Yukawa law on the resident points (FORCE_LAW_BODY: fp64 only, no
