@@ -445,6 +445,28 @@ int rmb_pair_histogram_device(rmb_ctx* ctx, double r_max, long n_bins, unsigned 
 int rmb_pair_histogram(rmb_ctx* ctx, double r_max, long n_bins, unsigned long long* hist_host);
 int rmb_pair_histogram_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, double r_max,
                                      long n_bins, unsigned long long* hist_dev);
+/* Sums behind the 6 x 6 translational-rotational mean-square displacement of rigid-body trajectories (the reference's
+ * general_application_utils.py: calc_total_msd_from_matrix_and_center / calc_msd_data_from_trajectory).  frames = (n_frames,
+ * n_bodies, 7) packed doubles, one row x y z s p1 p2 p3 per body (quaternion scalar part first, used as it is, never
+ * renormalised); offsets = (n_bodies, 3) body-frame tracking offsets p_b or NULL: the tracked point is c_b(f) = x_b(f) +
+ * R(q_b(f)) p_b with the reference's rotation matrix.  For every origin o in [o_begin, o_end), lag l in [0, n_lags) with
+ * o + l < n_frames, and body b:
+ *   Delta = [ c_b(o + l) - c_b(o) ;  u ],   u = 2 s_rel v_rel,   (s_rel, v_rel) = q_b(o + l) (x) conj(q_b(o)),
+ * which for unit quaternions is the reference's 1/2 sum_i (R(q(o)) e_i) x (R(q(o + l)) e_i); sums[l] += Delta Delta^T, sums =
+ * (n_lags, 6, 6) doubles, both triangles.  Origins whose lag does not exist add nothing; the number of terms per lag follows from
+ * the shapes and is the caller's to compute.  A record pass (tracked point and quaternion once per frame and body, body-major),
+ * a sweep in which a lane owns a lag and keeps its 21 sums in registers, and a finishing launch that adds the workgroups'
+ * partials in a fixed order: no atomics, the same bits for the same call.  origin_chunk: origins staged per window, 0 = planned
+ * (values above 1024 are cut to 1024).  Always fp64, single device.  It reads and writes nothing of the resident configuration
+ * (only the context's device, stream and a workspace of its own).
+ *   rmb_msd_frames_device  ADDS into sums_dev (the caller zeroes it and may accumulate calls), asynchronous on the context's stream;
+ *   rmb_msd_frames         host pointers; zeroes sums_host first; synchronous.
+ * RMB_ERR_ARG, before the device is touched: a null context / sums / frames pointer, negative sizes, n_lags < 1, origin_chunk < 0,
+ * or not 0 <= o_begin <= o_end <= n_frames.  n_frames = 0, n_bodies = 0 and o_begin = o_end leave the sums unchanged. */
+int rmb_msd_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n_bodies, const double* offsets_dev_or_null,
+                          long n_lags, long o_begin, long o_end, long origin_chunk, double* sums_dev);
+int rmb_msd_frames(rmb_ctx* ctx, const double* frames_host, long n_frames, long n_bodies, const double* offsets_host_or_null,
+                   long n_lags, long o_begin, long o_end, long origin_chunk, double* sums_host);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

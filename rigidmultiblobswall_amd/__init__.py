@@ -20,6 +20,7 @@ callers built on the path, each mirroring the reference module of th
   __main__.py          python -m rigidmultiblobswall_amd --input-file deck
   mcmc.py              MCMCSampler: Metropolis sampler of rigid-body configurations, python -m rigidmultiblobswall_amd.mcmc deck
   correlation.py       RadialDistribution: g(r) from the HIP pair-distance histogram, python -m rigidmultiblobswall_amd.correlation
+  msd.py               MeanSquareDisplacement: 6 x 6 translational-rotational MSD from the HIP lag sweep, python -m rigidmultiblobswall_amd.msd
 """
 from . import _lib  # noqa: F401
 from .context import MobilityContext  # noqa: F401

@@ -81,6 +81,8 @@ SYMBOLS = {
     "rmb_pair_histogram": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_long, _vp]),
     "rmb_pair_histogram_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_long, _vp]),
     "rmb_pair_histogram_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp, ctypes.c_double, ctypes.c_long, _vp]),
+    "rmb_msd_frames": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp] + [ctypes.c_long] * 4 + [_vp]),
+    "rmb_msd_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp] + [ctypes.c_long] * 4 + [_vp]),
     "rmb_mcmc_propose_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_double, _vp, _vp, _vp]),
     "rmb_mcmc_body_delta_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp] + [ctypes.c_double] * 6 +

@@ -579,6 +579,39 @@ class MobilityContext(object):
                                                           ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
     return out
 
+  def msd_frames_device(self, frames, n_lags, offsets=None, origins="window", out=None, origin_chunk=0):
+    """Sums behind the 6 x 6 mean-square displacement of `frames`, a contiguous CUDA float64 tensor (n_frames, n_bodies, 7) of
+    rows x y z s p1 p2 p3 (rmb_msd_frames_device): for every origin o, lag l < n_lags and body, Delta Delta^T with Delta =
+    [c(o + l) - c(o); u], c = x + R(q) p_b the tracked point (offsets: (n_bodies, 3) body-frame offsets, CUDA tensor or
+    array; None: the body's location) and u the reference's rotational displacement.  Quaternions are used as they are and
+    never renormalised.  origins="window": only origins for which all n_lags lags exist (the reference's); "all": lag l uses
+    every origin with o + l < n_frames.  The sums are ADDED to out=, a contiguous CUDA float64 tensor (n_lags, 6, 6) (None: a
+    new tensor of zeros).  origin_chunk: origins per staged window, 0 = planned.  Returns (sums, counts): counts is a numpy
+    int64 array of the number of terms per lag, computed from the shapes.  Asynchronous on torch's stream; the resident
+    configuration is neither read nor changed."""
+    import torch
+    if not _is_torch_cuda(frames) or frames.dtype != torch.float64 or not frames.is_contiguous() or frames.dim() != 3 or frames.shape[-1] != 7:
+      raise ValueError("frames must be a contiguous CUDA float64 tensor of shape (n_frames, n_bodies, 7)")
+    n_frames, n_bodies, n_lags = int(frames.shape[0]), int(frames.shape[1]), int(n_lags)
+    from .msd import counts_per_lag
+    counts = counts_per_lag(n_frames, n_bodies, n_lags, origins)      # checks n_lags and origins
+    if offsets is not None:
+      if not isinstance(offsets, torch.Tensor):
+        offsets = torch.from_numpy(_as_f64(offsets, 3 * n_bodies)).to(frames.device)
+      if not (offsets.is_cuda and offsets.dtype == torch.float64 and offsets.is_contiguous() and offsets.numel() == 3 * n_bodies):
+        raise ValueError("offsets must hold (n_bodies, 3) float64 values")
+    if out is None:
+      out = torch.zeros((n_lags, 6, 6), dtype=torch.float64, device=frames.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+              tuple(out.shape) == (n_lags, 6, 6)):
+      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_lags, 6, 6)")
+    o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_msd_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n_bodies,
+                                               ctypes.c_void_p(offsets.data_ptr()) if offsets is not None and offsets.numel() else None,
+                                               n_lags, 0, o_end, int(origin_chunk), ctypes.c_void_p(out.data_ptr())))
+    return out, counts
+
   @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""

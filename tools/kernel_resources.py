@@ -10,6 +10,8 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py --moves          body_delta_kernel / move_finish_kernel (rmb_mcmc_moves.hip), every pair loop
   python tools/kernel_resources.py --pair-hist      pair_hist_kernel (rmb_pair_hist.hip) next to potential_kernel; `lds` is the static part
                                                     (the staging slabs), the counters add 4 n_bins bytes of dynamic LDS
+  python tools/kernel_resources.py --msd             msd_record_kernel / msd_sweep_kernel / msd_finish_kernel (rmb_msd.hip); the sweep's LDS is
+                                                    dynamic: 56 (origin_chunk + 63) bytes, at least 10 752
   python tools/kernel_resources.py --rigid [TREE]   the dense per-body blocks and the finishing launches of the rigid-body
                                                     operator / Lanczos step (rmb_rigid.hip), every boundary instance
 """
@@ -89,6 +91,7 @@ def pair_loops(asm, mangled, floor=30):
 
 POTENTIAL_KERNELS = (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel"))
 PAIR_HIST_KERNELS = (("rmb_pair_hist.hip", "pair_hist_kernel"), ("rmb_potential.hip", "potential_kernel"))
+MSD_KERNELS = (("rmb_msd.hip", "msd_"),)
 MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
 
 
@@ -115,6 +118,9 @@ if __name__ == "__main__":
     sys.exit(0)
   if "--moves" in sys.argv:
     potential_table(isa_stats.ROOT, MOVE_KERNELS)
+    sys.exit(0)
+  if "--msd" in sys.argv:
+    potential_table(isa_stats.ROOT, MSD_KERNELS)
     sys.exit(0)
   if "--pair-hist" in sys.argv:
     potential_table(isa_stats.ROOT, PAIR_HIST_KERNELS)
