@@ -20,7 +20,9 @@ struct Geom {
   double Rz, iR, iR2;     // image separation R = (dx, dy, z_i + z_j); wall / free-surface operations only
 };
 
-template <bool IMAGE>
+// ZI2: `zi` carries the DOUBLED target height h = 2 z_i (wall-tt symmetric sweeps, sym_kernels.h: the lane keeps h, so the
+// 2 z_i of Q3 costs nothing).  2 z and 0.5 (2 z) are exact, so fma(h, 0.5, z_j) rounds once, to fl(z_i + z_j): the same bits.
+template <bool IMAGE, bool ZI2 = false>
 __device__ __forceinline__ Geom make_geom(double dx, double dy, double dz, double zi, double zj) {
   Geom g;
   g.dx = dx; g.dy = dy; g.dz = dz;
@@ -29,7 +31,7 @@ __device__ __forceinline__ Geom make_geom(double dx, double dy, double dz, doubl
   g.ir = rsqrt_f64(g.r2);
   g.ir2 = g.ir * g.ir;
   if constexpr (IMAGE) {
-    g.Rz = zi + zj;
+    g.Rz = ZI2 ? __builtin_fma(zi, 0.5, zj) : zi + zj;
     g.iR = rsqrt_f64(__builtin_fma(g.Rz, g.Rz, g.rho2));
     g.iR2 = g.iR * g.iR;
   } else {
@@ -125,7 +127,7 @@ __device__ __forceinline__ void block_apply(const BlockM& m, const Geom& g, cons
 // parity test).
 typedef BlockM TTc;
 
-template <bool WALL>
+template <bool WALL, bool ZI2 = false>
 __device__ __forceinline__ TTc tt_block(const PairConsts& k, const Geom& g, double zi, double zj, double cF, double cD) {
   TTc m;
   if constexpr (WALL) {
@@ -144,7 +146,8 @@ __device__ __forceinline__ TTc tt_block(const PairConsts& k, const Geom& g, doub
     const double H = __builtin_fma(Tc, __builtin_fma(p30, k.m7, 48.0), __builtin_fma(Tq, p30, __builtin_fma(om, -1.5, 1.0)));
     const double cDdz = cD * g.dz;
     // Q3 = cD d_z + s q (R_z H - 2 z_i): 2 z_i does not change along a lane's row of pairs (hoisted);  Q3 + Q4 = 2 (cD - s q) d_z
-    m.Q3 = __builtin_fma(q3, __builtin_fma(g.Rz, H, -(zi + zi)), cDdz);
+    // (ZI2: the caller holds 2 z_i itself -- a source modifier instead of a v_add_f64 per pair)
+    m.Q3 = __builtin_fma(q3, __builtin_fma(g.Rz, H, ZI2 ? -zi : -(zi + zi)), cDdz);
     m.Q4 = __builtin_fma(__builtin_fma(-q3, g.dz, cDdz), 2.0, -m.Q3);
     m.P = __builtin_fma(-q3, __builtin_fma(Tc, -60.0, H), cD);                     // H - 20 T^2/3
     const double G1 = __builtin_fma(Tc, p30, __builtin_fma(Tq, __builtin_fma(U, k.m6, 2.0), __builtin_fma(om, 0.5, 1.0)));
@@ -160,10 +163,10 @@ __device__ __forceinline__ TTc tt_block(const PairConsts& k, const Geom& g, doub
   return m;
 }
 
-template <bool WALL>
+template <bool WALL, bool ZI2 = false>
 __device__ __forceinline__ TTc tt_coeffs(const PairConsts& k, const Geom& g, double zi, double zj) {
   const Rpy p = rpy_coeffs<true, false, false>(k, g);
-  return tt_block<WALL>(k, g, zi, zj, p.cF, p.cD);
+  return tt_block<WALL, ZI2>(k, g, zi, zj, p.cF, p.cD);
 }
 
 // ui += M_tt,ij vj ;  t (+)= M_tt,ji vi
@@ -353,11 +356,11 @@ __device__ __forceinline__ void pair_coupling_forward(const PairConsts& k, doubl
 }
 
 // One-sided tt through the same closed-form block (forward direction only; the reversed one is dead code)
-template <bool WALL>
+template <bool WALL, bool ZI2 = false>
 __device__ __forceinline__ void pair_tt_forward(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
                                                 double vx, double vy, double vz, Vec3& u) {
-  const Geom g = make_geom<WALL>(dx, dy, dz, zi, zj);
-  const TTc c = tt_coeffs<WALL>(k, g, zi, zj);
+  const Geom g = make_geom<WALL, ZI2>(dx, dy, dz, zi, zj);
+  const TTc c = tt_coeffs<WALL, ZI2>(k, g, zi, zj);
   const double vi[3] = {0.0, 0.0, 0.0}, vj[3] = {vx, vy, vz};
   double u3[3] = {u.x, u.y, u.z}, t[3];
   tt_apply<WALL, false>(c, g, vi, vj, u3, t);
@@ -486,12 +489,13 @@ __device__ __forceinline__ void free_surface_forward(const PairConsts& k, double
   u.x = o[0]; u.y = o[1]; u.z = o[2];
 }
 
-template <int KIND, bool WALL>
+template <int KIND, bool WALL, bool ZI2 = false>
 __device__ __forceinline__ void pair_apply(const PairConsts& k, double dx, double dy, double dz, double zi,
                                            double zj, double vx, double vy, double vz, double wx, double wy,
                                            double wz, Vec3& u) {
+  static_assert(!ZI2 || (KIND == KIND_TT && WALL), "doubled heights: wall tt only (every other kind reads z_i itself)");
   const double Rz = zi + zj;
-  if constexpr (KIND == KIND_TT) pair_tt_forward<WALL>(k, dx, dy, dz, zi, zj, vx, vy, vz, u);
+  if constexpr (KIND == KIND_TT) pair_tt_forward<WALL, ZI2>(k, dx, dy, dz, zi, zj, vx, vy, vz, u);
   if constexpr (KIND == KIND_TR) pair_coupling_forward<true, WALL>(k, dx, dy, dz, zi, zj, vx, vy, vz, u);
   if constexpr (KIND == KIND_RT) pair_coupling_forward<false, WALL>(k, dx, dy, dz, zi, zj, vx, vy, vz, u);
   if constexpr (KIND == KIND_RR) pair_rr<WALL>(k, dx, dy, dz, Rz, vx, vy, vz, u);

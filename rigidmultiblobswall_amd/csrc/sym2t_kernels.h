@@ -28,6 +28,8 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
   double2* rec = rec_all[wave];
   double* accj = accj_all[wave];
   const char* rec_bytes = reinterpret_cast<const char*>(rec);
+  // wall tt: z0 / z1 hold the DOUBLED heights 2 z_i (sym_kernels.h: kSymZi2) -- same bits, one v_add_f64 less per pair
+  constexpr bool Z2 = kSymZi2<KIND, WALL>;
 
   const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
   // diagnostics build only (option "wave_clock"): wall-clock start / end of the wave and the shader-clock cycles it spends
@@ -46,8 +48,8 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
   int p_cur = -1;
   long i0 = 0, i1 = 0;
   bool ok0 = false, ok1 = false;
-  double x0 = 0, y0 = 0, z0 = 1.0, v0x = 0, v0y = 0, v0z = 0;
-  double x1 = 0, y1 = 0, z1 = 1.0, v1x = 0, v1y = 0, v1z = 0;
+  double x0 = 0, y0 = 0, z0 = sym_height<Z2>(1.0), v0x = 0, v0y = 0, v0z = 0;
+  double x1 = 0, y1 = 0, z1 = sym_height<Z2>(1.0), v1x = 0, v1y = 0, v1z = 0;
   Vec3 u0 = {0.0, 0.0, 0.0}, u1 = {0.0, 0.0, 0.0};
 
   auto flush_rows = [&]() {
@@ -76,16 +78,16 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
       i0 = 64L * (2 * p) + lane;
       i1 = i0 + 64;
       ok0 = i0 < a.n; ok1 = i1 < a.n;
-      x0 = 1e100; y0 = 1e100; z0 = 1.0; v0x = 0; v0y = 0; v0z = 0;
-      x1 = 1e100; y1 = 1e100; z1 = 1.0; v1x = 0; v1y = 0; v1z = 0;
+      x0 = 1e100; y0 = 1e100; z0 = sym_height<Z2>(1.0); v0x = 0; v0y = 0; v0z = 0;
+      x1 = 1e100; y1 = 1e100; z1 = sym_height<Z2>(1.0); v1x = 0; v1y = 0; v1z = 0;
       if (ok0) {
         const double4 q = a.pos[i0];
-        x0 = q.x; y0 = q.y; z0 = q.z;
+        x0 = q.x; y0 = q.y; z0 = sym_height<Z2>(q.z);
         v0x = a.vec[3 * i0] * q.w; v0y = a.vec[3 * i0 + 1] * q.w; v0z = a.vec[3 * i0 + 2] * q.w;
       }
       if (ok1) {
         const double4 q = a.pos[i1];
-        x1 = q.x; y1 = q.y; z1 = q.z;
+        x1 = q.x; y1 = q.y; z1 = sym_height<Z2>(q.z);
         v1x = a.vec[3 * i1] * q.w; v1y = a.vec[3 * i1 + 1] * q.w; v1z = a.vec[3 * i1 + 2] * q.w;
       }
       u0.x = 0.0; u0.y = 0.0; u0.z = 0.0;
@@ -119,8 +121,8 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
         // the second pair ACCUMULATES its transposed rows into the first one's (the multiplies that start them become fused
         // multiply-adds: three v_add_f64 less per step than summing two finished contributions)
         double ax, ay, az;
-        pair_sym<KIND, WALL>(a.k, x0 - q0.x, y0 - q0.y, z0 - q1.x, z0, q1.x, v0x, v0y, v0z, q1.y, q2.x, q2.y, u0, ax, ay, az);
-        pair_sym<KIND, WALL, true>(a.k, x1 - q0.x, y1 - q0.y, z1 - q1.x, z1, q1.x, v1x, v1y, v1z, q1.y, q2.x, q2.y, u1, ax, ay, az);
+        pair_sym<KIND, WALL, false, Z2>(a.k, x0 - q0.x, y0 - q0.y, sym_dz<Z2>(z0, q1.x), z0, q1.x, v0x, v0y, v0z, q1.y, q2.x, q2.y, u0, ax, ay, az);
+        pair_sym<KIND, WALL, true, Z2>(a.k, x1 - q0.x, y1 - q0.y, sym_dz<Z2>(z1, q1.x), z1, q1.x, v1x, v1y, v1z, q1.y, q2.x, q2.y, u1, ax, ay, az);
         __hip_atomic_fetch_add(&accj[jj], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __hip_atomic_fetch_add(&accj[64 + jj], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __hip_atomic_fetch_add(&accj[128 + jj], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
           const int jj = (lane + k) & 63;
           const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
           const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-          pair_apply<KIND, WALL>(a.k, x0 - q0.x, y0 - q0.y, z0 - q1.x, z0, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, u0);
+          pair_apply<KIND, WALL, Z2>(a.k, x0 - q0.x, y0 - q0.y, sym_dz<Z2>(z0, q1.x), z0, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, u0);
         }
       } else {
         for (int k = kb; k < k1; ++k) {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
           const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
           const double2 q0 = r[0], q1 = r[1], q2 = r[2];
           double tx, ty, tz;
-          pair_sym<KIND, WALL>(a.k, x0 - q0.x, y0 - q0.y, z0 - q1.x, z0, q1.x, v0x, v0y, v0z, q1.y, q2.x, q2.y, u0, tx, ty, tz);
+          pair_sym<KIND, WALL, false, Z2>(a.k, x0 - q0.x, y0 - q0.y, sym_dz<Z2>(z0, q1.x), z0, q1.x, v0x, v0y, v0z, q1.y, q2.x, q2.y, u0, tx, ty, tz);
           __hip_atomic_fetch_add(&accj[jj], tx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           __hip_atomic_fetch_add(&accj[64 + jj], ty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           __hip_atomic_fetch_add(&accj[128 + jj], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
           const int jj = (lane + k) & 63;
           const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
           const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-          pair_apply<KIND, WALL>(a.k, x1 - q0.x, y1 - q0.y, z1 - q1.x, z1, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, u1);
+          pair_apply<KIND, WALL, Z2>(a.k, x1 - q0.x, y1 - q0.y, sym_dz<Z2>(z1, q1.x), z1, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, u1);
         }
       }
     }

@@ -33,6 +33,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const char* rec_bytes = reinterpret_cast<const char*>(rec);
+  constexpr bool Z2 = kSymZi2<KIND, WALL>;      // wall tt: zi holds the doubled height 2 z_i (sym_kernels.h: pair_sym)
 
   // a.steps_per_wave carries the steps per WORKGROUP here (rmb_sym.hip)
   // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
 
   int I_cur = -1;
   long i = 0;
-  double xi = 0, yi = 0, zi = 1.0, vix = 0, viy = 0, viz = 0;
+  double xi = 0, yi = 0, zi = sym_height<Z2>(1.0), vix = 0, viy = 0, viz = 0;
 
   while (s < s_end) {
     const int k0 = (int)(s & 63);
@@ -69,10 +70,10 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
       }
       I_cur = I;
       i = 64L * I + lane;
-      xi = 1e100; yi = 1e100; zi = 1.0; vix = 0; viy = 0; viz = 0;
+      xi = 1e100; yi = 1e100; zi = sym_height<Z2>(1.0); vix = 0; viy = 0; viz = 0;
       if (i < a.n) {
         const double4 p = a.pos[i];
-        xi = p.x; yi = p.y; zi = p.z;
+        xi = p.x; yi = p.y; zi = sym_height<Z2>(p.z);
         vix = a.vec[3 * i] * p.w; viy = a.vec[3 * i + 1] * p.w; viz = a.vec[3 * i + 2] * p.w;
       }
     }
@@ -103,10 +104,10 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
         const int jj = (lane + k) & 63;
         const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
         const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = zi - q1.x;
+        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
         double tx, ty, tz;
         if constexpr (!PERIODIC) {
-          pair_sym<KIND, WALL>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
+          pair_sym<KIND, WALL, false, Z2>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
         } else {
           if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
           if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
           for (int bx = -px; bx <= px; ++bx)
             for (int by = -py; by <= py; ++by)
               for (int bz = -pz; bz <= pz; ++bz) {
-                pair_sym<KIND, WALL, true>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
+                pair_sym<KIND, WALL, true, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
                                            q2.y, ui, tx, ty, tz);      // accumulates (fused multiply-adds)
               }
         }
@@ -130,9 +131,9 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
         const int jj = (lane + k) & 63;
         const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
         const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = zi - q1.x;
+        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
         if constexpr (!PERIODIC) {
-          pair_apply<KIND, WALL>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
+          pair_apply<KIND, WALL, Z2>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
         } else {
           if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
           if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
             for (int by = -py; by <= py; ++by)
               for (int bz = -pz; bz <= pz; ++bz) {
                 if (k == 0 && bx == 0 && by == 0 && bz == 0) continue;
-                pair_apply<KIND, WALL>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
+                pair_apply<KIND, WALL, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
                                        0.0, ui);
               }
         }

@@ -61,12 +61,12 @@ constexpr int kSymRecBytes = 48;
 // (BlockM: F, P, Q3, Q4, Szz) and contracted with ten instructions per direction.
 // ACC: the transposed rows are ADDED to (tx, ty, tz) instead of written -- the second target blob of sym2t_kernel folds its
 // contribution into the first one's with the fused multiply-adds that build it (three v_add_f64 less per rotation step).
-template <bool WALL, bool ACC = false>
+template <bool WALL, bool ACC = false, bool ZI2 = false>
 __device__ __forceinline__ void pair_tt_sym(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
                                             double vix, double viy, double viz, double vjx, double vjy, double vjz,
                                             Vec3& ui, double& tx, double& ty, double& tz) {
-  const Geom g = make_geom<WALL>(dx, dy, dz, zi, zj);
-  const TTc c = tt_coeffs<WALL>(k, g, zi, zj);
+  const Geom g = make_geom<WALL, ZI2>(dx, dy, dz, zi, zj);
+  const TTc c = tt_coeffs<WALL, ZI2>(k, g, zi, zj);
   const double vi[3] = {vix, viy, viz}, vj[3] = {vjx, vjy, vjz};
   double u[3] = {ui.x, ui.y, ui.z}, t[3];
   if constexpr (ACC) { t[0] = tx; t[1] = ty; t[2] = tz; }
@@ -109,12 +109,23 @@ __device__ __forceinline__ void pair_coupling_sym(const PairConsts& k, double dx
   tx = t[0]; ty = t[1]; tz = t[2];
 }
 
+// Doubled-height operands.  The wall tt block needs 2 z_i (Q3, pair_blocks.h: tt_block); at the 128-register cap the compiler
+// rebuilt it for every pair.  The wall-tt instances of sym_kernel, sym_coop_kernel and sym2t_kernel therefore keep h = 2 z_i in the
+// lane where the other kinds keep z_i (padding sentinel 2.0 for 1.0) and hand it on as `zi` with ZI2 set:
+//   d_z = fma(h, 0.5, -z_j),  R_z = fma(h, 0.5, z_j),  the -2 z_i of Q3 = -h (a source modifier).
+// 2 z and 0.5 (2 z) are exact and each fma rounds once, so every pair block is bit for bit what z_i gives.  tr / rt anchor on
+// z_i itself and rr does not need 2 z_i: they keep z_i.
+template <int KIND, bool WALL> constexpr bool kSymZi2 = KIND == KIND_TT && WALL;
+template <bool ZI2> __device__ __forceinline__ double sym_height(double z) { return ZI2 ? z + z : z; }           // what the lane keeps
+template <bool ZI2> __device__ __forceinline__ double sym_dz(double zi, double zj) { return ZI2 ? __builtin_fma(zi, 0.5, -zj) : zi - zj; }
+
 // dispatcher
-template <int KIND, bool WALL, bool ACC = false>
+template <int KIND, bool WALL, bool ACC = false, bool ZI2 = false>
 __device__ __forceinline__ void pair_sym(const PairConsts& k, double dx, double dy, double dz, double zi, double zj,
                                          double vix, double viy, double viz, double vjx, double vjy, double vjz,
                                          Vec3& ui, double& tx, double& ty, double& tz) {
-  if constexpr (KIND == KIND_TT) pair_tt_sym<WALL, ACC>(k, dx, dy, dz, zi, zj, vix, viy, viz, vjx, vjy, vjz, ui, tx, ty, tz);
+  static_assert(!ZI2 || (KIND == KIND_TT && WALL), "doubled heights: wall tt only");
+  if constexpr (KIND == KIND_TT) pair_tt_sym<WALL, ACC, ZI2>(k, dx, dy, dz, zi, zj, vix, viy, viz, vjx, vjy, vjz, ui, tx, ty, tz);
   if constexpr (KIND == KIND_RR) pair_rr_sym<WALL, ACC>(k, dx, dy, dz, zi, zj, vix, viy, viz, vjx, vjy, vjz, ui, tx, ty, tz);
   if constexpr (KIND == KIND_TR) pair_coupling_sym<true, WALL, ACC>(k, dx, dy, dz, zi, zj, vix, viy, viz, vjx, vjy, vjz, ui, tx, ty, tz);
   if constexpr (KIND == KIND_RT) pair_coupling_sym<false, WALL, ACC>(k, dx, dy, dz, zi, zj, vix, viy, viz, vjx, vjy, vjz, ui, tx, ty, tz);
@@ -130,6 +141,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
   double2* rec = rec_all[wave];
   double* accj = accj_all[wave];
   const char* rec_bytes = reinterpret_cast<const char*>(rec);
+  constexpr bool Z2 = kSymZi2<KIND, WALL>;      // wall tt: zi holds the doubled height 2 z_i (see pair_sym)
 
   // Static, exactly balanced schedule: the n_units * 64 rotation steps are cut into gridDim.x * 4 equal
   // contiguous ranges, one per wave; a range may begin and end inside a unit.
@@ -151,7 +163,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
   int I_cur = -1;
   long i = 0;
   bool vi_ok = false;
-  double xi = 0, yi = 0, zi = 1.0, vix = 0, viy = 0, viz = 0;
+  double xi = 0, yi = 0, zi = sym_height<Z2>(1.0), vix = 0, viy = 0, viz = 0;
   Vec3 ui = {0.0, 0.0, 0.0};
 
   while (s < s_end) {
@@ -169,10 +181,10 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
       I_cur = I;
       i = 64L * I + lane;
       vi_ok = i < a.n;
-      xi = 1e100; yi = 1e100; zi = 1.0; vix = 0; viy = 0; viz = 0;
+      xi = 1e100; yi = 1e100; zi = sym_height<Z2>(1.0); vix = 0; viy = 0; viz = 0;
       if (vi_ok) {
         const double4 p = a.pos[i];
-        xi = p.x; yi = p.y; zi = p.z;
+        xi = p.x; yi = p.y; zi = sym_height<Z2>(p.z);
         vix = a.vec[3 * i] * p.w; viy = a.vec[3 * i + 1] * p.w; viz = a.vec[3 * i + 2] * p.w;
       }
       ui.x = 0.0; ui.y = 0.0; ui.z = 0.0;
@@ -204,10 +216,10 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
         const int jj = (lane + k) & 63;
         const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
         const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = zi - q1.x;
+        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
         double tx, ty, tz;
         if constexpr (!PERIODIC) {
-          pair_sym<KIND, WALL>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
+          pair_sym<KIND, WALL, false, Z2>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
         } else {
           if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
           if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
@@ -216,7 +228,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
           for (int bx = -px; bx <= px; ++bx)
             for (int by = -py; by <= py; ++by)
               for (int bz = -pz; bz <= pz; ++bz) {
-                pair_sym<KIND, WALL, true>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
+                pair_sym<KIND, WALL, true, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
                                            q2.y, ui, tx, ty, tz);      // accumulates (fused multiply-adds)
               }
         }
@@ -240,9 +252,9 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
         const int jj = (lane + k) & 63;
         const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
         const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = zi - q1.x;
+        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
         if constexpr (!PERIODIC) {
-          pair_apply<KIND, WALL>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
+          pair_apply<KIND, WALL, Z2>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
         } else {
           if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
           if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
             for (int by = -py; by <= py; ++by)
               for (int bz = -pz; bz <= pz; ++bz) {
                 if (k == 0 && bx == 0 && by == 0 && bz == 0) continue;
-                pair_apply<KIND, WALL>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
+                pair_apply<KIND, WALL, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
                                        0.0, ui);
               }
         }

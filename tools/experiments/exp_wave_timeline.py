@@ -75,6 +75,11 @@ print("SIMDs used %d, waves per SIMD histogram %s; CUs used %d" % (len(u), dict(
 simd_end = np.array([end[key_simd == k].max() for k in u]); simd_start = np.array([start[key_simd == k].min() for k in u])
 print("per SIMD: first wave starts p50 %.2f max %.2f | last wave ends p1 %.2f p50 %.2f max %.2f us" %
       (np.median(simd_start), simd_start.max(), np.percentile(simd_end, 1), np.median(simd_end), simd_end.max()))
+# what a dynamic hand-out of the last steps could recover at most: every SIMD waits for the slowest one
+print("per SIMD: last wave ends mean %.2f p50 %.2f max %.2f us | (max - mean) / span = %.4f" %
+      (simd_end.mean(), np.median(simd_end), simd_end.max(), (simd_end.max() - simd_end.mean()) / span))
+xcc_of = np.array([xcc[key_simd == k][0] for k in u])
+print("per XCD : mean end of its SIMDs " + " ".join("%d:%.1f" % (x, simd_end[xcc_of == x].mean()) for x in np.unique(xcc_of)))
 if ph is not None:
   stage, total = ph[:, 0].astype(np.float64), ph[:, 1].astype(np.float64)
   ok = total > 0

@@ -12,6 +12,9 @@ residency, so a change that moves an instance across a register or LDS boundary 
                                                     (the staging slabs), the counters add 4 n_bins bytes of dynamic LDS
   python tools/kernel_resources.py --msd             msd_record_kernel / msd_sweep_kernel / msd_finish_kernel (rmb_msd.hip); the sweep's LDS is
                                                     dynamic: 56 (origin_chunk + 63) bytes, at least 10 752
+  python tools/kernel_resources.py --sym OTHER_TREE every kernel of the units that see pair_blocks.h / sym_kernels.h (symmetric families, fp32
+                                                    twins, one-sided sweeps): OTHER_TREE | this tree, resources and every pair loop, differing
+                                                    rows marked and counted -- what a change to the shared pair arithmetic touched
   python tools/kernel_resources.py --rigid [TREE]   the dense per-body blocks and the finishing launches of the rigid-body
                                                     operator / Lanczos step (rmb_rigid.hip), every boundary instance
 """
@@ -112,7 +115,42 @@ def potential_table(root, kernels=POTENTIAL_KERNELS):
       print("%-44s vgpr %3d sgpr %3d scratch %d lds %5d res %d code %4d  %s" % (name, vgpr, sgpr, scratch, lds, resident(vgpr, lds), code, loops))
 
 
+SYM_UNITS = ("rmb_sym.hip", "rmb_symx2t.hip", "rmb_symx2t_per.hip", "rmb_symx_coop.hip", "rmb_sym32.hip", "rmb_sweep.hip")
+
+
+def sym_table(root):
+  """name -> resources + every pair loop, for every kernel of SYM_UNITS (units compiled in parallel)."""
+  from concurrent.futures import ThreadPoolExecutor
+
+  def one(unit):
+    return subprocess.run([isa_stats.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-S",
+                           "--cuda-device-only", "-o", "-", os.path.join(root, "rigidmultiblobswall_amd", "csrc", unit)],
+                          check=True, capture_output=True, text=True).stdout
+  with ThreadPoolExecutor(max_workers=len(SYM_UNITS)) as pool:
+    asms = list(pool.map(one, SYM_UNITS))
+  rows = {}
+  for asm in asms:
+    found = list(INFO.finditer(asm))
+    names = subprocess.run(["c++filt"], input="\n".join(m.group(1) for m in found), capture_output=True, text=True).stdout.split("\n")
+    for m, name in zip(found, names):
+      name = re.sub(r"\)$", "", re.sub(r"\((rmb::)?\w+( const)?\)$", "", name.strip().replace("(anonymous namespace)::", "").replace("void ", "")))
+      code, sgpr, vgpr, scratch, lds = (int(g) for g in m.groups()[1:])
+      loops = " ".join("%d/%d/%d" % l[1:] for l in pair_loops(asm, m.group(1)))
+      rows[name] = "vgpr %3d sgpr %3d scratch %3d lds %5d code %5d  loops %s" % (vgpr, sgpr, scratch, lds, code, loops)
+  return rows
+
+
 if __name__ == "__main__":
+  if "--sym" in sys.argv:
+    other, here = sym_table(sys.argv[sys.argv.index("--sym") + 1]), sym_table(isa_stats.ROOT)
+    changed = [n for n in sorted(set(here) | set(other)) if here.get(n) != other.get(n)]
+    for name in sorted(here):
+      print("%-70s %-72s | %s%s" % (name[:70], other.get(name, "-"), here[name], "   *" if name in changed else ""))
+    print("# %d kernels, %d differ (loops: VALU / fp64 VALU / LDS instructions of every inner loop with >= 30 VALU instructions)" %
+          (len(here), len(changed)))
+    for name in changed:
+      print("#   differs: %s" % name)
+    sys.exit(0)
   if "--potential" in sys.argv:
     potential_table(isa_stats.ROOT)
     sys.exit(0)
