@@ -467,6 +467,39 @@ int rmb_msd_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames,
                           long n_lags, long o_begin, long o_end, long origin_chunk, double* sums_dev);
 int rmb_msd_frames(rmb_ctx* ctx, const double* frames_host, long n_frames, long n_bodies, const double* offsets_host_or_null,
                    long n_lags, long o_begin, long o_end, long origin_chunk, double* sums_host);
+/* Density modes and the lag sums behind the structure factor S(k), the intermediate scattering function F(k, t) and its
+ * self part F_s(k, t) of point trajectories, by direct Fourier sums (no grid; what the reference delegated to HydroGrid,
+ * multi_bodies/multi_bodies.py: call_HydroGrid).  frames = (n_frames, n, 3) packed doubles on the device; L = 3 lengths on the
+ * host; kint = (K, 3) integers n on the host: k = 2 pi (n_x / L_x, n_y / L_y, n_z / L_z).  L_d is the period of a periodic
+ * direction (everything below is then invariant under wrapping) or any reference length of an open one; it may be <= 0
+ * only where every n_d = 0.  Phase of point j in turns: t_j = sum_d x_jd (n_d / L_d), with one division per axis and
+ * fused steps; theta_j = 2 pi (t_j - rint(t_j)), evaluated as sincospi(2 (t_j - rint(t_j))): the reduction is done in
+ * turns, so a cloud many periods from the origin keeps its accuracy.
+ *   rmb_density_modes_frames_device    modes[f, k] = (sum_j cos theta_j, -sum_j sin theta_j) = rho_k(f) = sum_j exp(-i theta_j);
+ *                                      modes_dev = (n_frames, K, 2), OVERWRITTEN.  A lane owns a wavevector, the points of a
+ *                                      frame are staged in LDS; few frames of many points are cut into point ranges whose
+ *                                      partials a finishing launch adds in a fixed order.
+ *   rmb_scattering_lags_device         C[l, k] = sum_o Re( rho_k(o + l) conj rho_k(o) ) over the modes (n_frames, K, 2);
+ *   rmb_self_scattering_frames_device  Sf[l, k] = sum_o sum_j cos( theta_j(o + l) - theta_j(o) ), computed as
+ *                                      Re( z_j(o + l) conj z_j(o) ), z = exp(-i theta), from per-point phase records of three
+ *                                      wavevectors per pass;
+ *                                      both for origins o in [o_begin, o_end), lags l in [0, n_lags) with o + l < n_frames,
+ *                                      ADDED to sums_dev = (n_lags, K) (the caller zeroes it and may accumulate calls).  A
+ *                                      lane owns a lag (the sweep of rmb_msd_frames_device), partials per workgroup, a
+ *                                      finishing launch.
+ * Normalisation is the caller's: S(k) = C[0, k] / (n n_origins), F(k, l) = C[l, k] / (n count[l]), F_s(k, l) = Sf[l, k] /
+ * (n count[l]).  No floating-point atomics: the same call gives the same bits.  Always fp64, single device, asynchronous
+ * on the context's stream.  Nothing of the resident configuration is read or written (only the context's device, stream
+ * and a workspace of these entries).
+ * RMB_ERR_ARG, before the device is touched: a null pointer (one whose array is empty may be null), negative sizes,
+ * n_lags < 1, not 0 <= o_begin <= o_end <= n_frames, K > 16384, |n_d| > 32768, n_d != 0 where L_d <= 0.  n_frames = 0, K = 0
+ * and o_begin = o_end leave the lag sums unchanged; n = 0 writes zero modes and adds nothing to the self sums. */
+int rmb_density_modes_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, const int* kint,
+                                    long K, double* modes_dev);
+int rmb_scattering_lags_device(rmb_ctx* ctx, const double* modes_dev, long n_frames, long K, long n_lags, long o_begin, long o_end,
+                               double* sums_dev);
+int rmb_self_scattering_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, const int* kint,
+                                      long K, long n_lags, long o_begin, long o_end, double* sums_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

@@ -21,6 +21,7 @@ callers built on the path, each mirroring the reference module of th
   mcmc.py              MCMCSampler: Metropolis sampler of rigid-body configurations, python -m rigidmultiblobswall_amd.mcmc deck
   correlation.py       RadialDistribution: g(r) from the HIP pair-distance histogram, python -m rigidmultiblobswall_amd.correlation
   msd.py               MeanSquareDisplacement: 6 x 6 translational-rotational MSD from the HIP lag sweep, python -m rigidmultiblobswall_amd.msd
+  scattering.py        IntermediateScattering: S(k), F(k, t), F_s(k, t) from the HIP Fourier sweeps, python -m rigidmultiblobswall_amd.scattering
 """
 from . import _lib  # noqa: F401
 from .context import MobilityContext  # noqa: F401

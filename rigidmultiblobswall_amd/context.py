@@ -613,6 +613,92 @@ class MobilityContext(object):
     return out, counts
 
   @staticmethod
+  def _scattering_frames(frames):
+    import torch
+    if not _is_torch_cuda(frames) or frames.dtype != torch.float64 or not frames.is_contiguous() or frames.dim() != 3 or frames.shape[-1] != 3:
+      raise ValueError("frames must be a contiguous CUDA float64 tensor of shape (n_frames, n, 3)")
+    return int(frames.shape[0]), int(frames.shape[1])
+
+  @staticmethod
+  def _scattering_wavevectors(periodic_length, wavevectors):
+    L = _as_f64(periodic_length, 3)
+    k = np.asarray(wavevectors)
+    if k.dtype.kind not in "iu" or k.ndim != 2 or k.shape[1] != 3:
+      raise ValueError("wavevectors must be an integer array of shape (K, 3)")
+    return L, np.ascontiguousarray(np.clip(k, -2 ** 30, 2 ** 30), dtype=np.int32)      # beyond int32: still beyond what the entry accepts
+
+  @staticmethod
+  def _scattering_out(out, n_lags, K, device):
+    import torch
+    if out is None:
+      return torch.zeros((n_lags, K), dtype=torch.float64, device=device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n_lags, K)):
+      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_lags, K)")
+    return out
+
+  def density_modes_frames_device(self, frames, periodic_length, wavevectors, out=None):
+    """Density modes rho_k(f) = sum_j exp(-i k . x_j(f)) of `frames`, a contiguous CUDA float64 tensor (n_frames, n, 3)
+    (rmb_density_modes_frames_device).  wavevectors: integer array (K, 3) of n, k = 2 pi n_d / L_d; periodic_length: the three
+    L_d (a period, or any reference length of an open direction; <= 0 only where every n_d = 0).  Returns a CUDA float64 tensor
+    (n_frames, K, 2) of (Re, Im) = (sum cos, -sum sin); out= (that shape, contiguous) is OVERWRITTEN.  Asynchronous on torch's
+    stream; the resident configuration is neither read nor changed."""
+    import torch
+    n_frames, n = self._scattering_frames(frames)
+    L, k = self._scattering_wavevectors(periodic_length, wavevectors)
+    K = int(k.shape[0])
+    if out is None:
+      out = torch.empty((n_frames, K, 2), dtype=torch.float64, device=frames.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+              tuple(out.shape) == (n_frames, K, 2)):
+      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_frames, K, 2)")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_density_modes_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
+                                                         _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K,
+                                                         ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
+
+  def scattering_lags_device(self, modes, n_lags, origins="window", out=None, o_begin=0, o_end=None):
+    """Collective lag sums C[l, k] = sum_o Re(rho_k(o + l) conj rho_k(o)) of `modes`, a contiguous CUDA float64 tensor
+    (n_frames, K, 2) (rmb_scattering_lags_device).  origins="window": only origins for which all n_lags lags exist; "all": lag
+    l uses every origin with o + l < n_frames; o_begin / o_end narrow the origins to [o_begin, o_end) (o_end=None: the
+    convention's last origin).  The sums are ADDED to out=, a contiguous CUDA float64 tensor (n_lags, K) (None: a new tensor of
+    zeros).  Returns (sums, counts): counts is msd.counts_per_lag for ONE point, the number of origins per lag of the whole
+    range (the caller's own count where o_begin / o_end are given).  Asynchronous on torch's stream."""
+    import torch
+    if not _is_torch_cuda(modes) or modes.dtype != torch.float64 or not modes.is_contiguous() or modes.dim() != 3 or modes.shape[-1] != 2:
+      raise ValueError("modes must be a contiguous CUDA float64 tensor of shape (n_frames, K, 2)")
+    n_frames, K, n_lags = int(modes.shape[0]), int(modes.shape[1]), int(n_lags)
+    from .msd import counts_per_lag
+    counts = counts_per_lag(n_frames, 1, n_lags, origins)      # checks n_lags and origins
+    out = self._scattering_out(out, n_lags, K, modes.device)
+    if o_end is None:
+      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_scattering_lags_device(self._h, ctypes.c_void_p(modes.data_ptr()) if modes.numel() else None, n_frames, K, n_lags,
+                                                    int(o_begin), int(o_end), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out, counts
+
+  def self_scattering_frames_device(self, frames, periodic_length, wavevectors, n_lags, origins="window", out=None, o_begin=0, o_end=None):
+    """Self lag sums Sf[l, k] = sum_o sum_j cos(k . (x_j(o + l) - x_j(o))) of `frames`, a contiguous CUDA float64 tensor
+    (n_frames, n, 3) (rmb_self_scattering_frames_device); wavevectors and periodic_length as density_modes_frames_device,
+    origins, o_begin, o_end and out= (n_lags, K), ADDED to, as scattering_lags_device.  Returns (sums, counts), counts the
+    origins per lag as there (a lag's sum has n times as many terms).  Asynchronous on torch's stream; the resident configuration is neither
+    read nor changed."""
+    n_frames, n = self._scattering_frames(frames)
+    L, k = self._scattering_wavevectors(periodic_length, wavevectors)
+    K, n_lags = int(k.shape[0]), int(n_lags)
+    from .msd import counts_per_lag
+    counts = counts_per_lag(n_frames, 1, n_lags, origins)
+    out = self._scattering_out(out, n_lags, K, frames.device)
+    if o_end is None:
+      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_self_scattering_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
+                                                           _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K, n_lags, int(o_begin),
+                                                           int(o_end), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out, counts
+
+  @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""
     try:

@@ -12,6 +12,8 @@ residency, so a change that moves an instance across a register or LDS boundary 
                                                     (the staging slabs), the counters add 4 n_bins bytes of dynamic LDS
   python tools/kernel_resources.py --msd             msd_record_kernel / msd_sweep_kernel / msd_finish_kernel (rmb_msd.hip); the sweep's LDS is
                                                     dynamic: 56 (origin_chunk + 63) bytes, at least 10 752
+  python tools/kernel_resources.py --scattering      scat_modes_kernel / scat_record_kernel / scat_sweep_kernel and their finishing launches
+                                                    (rmb_scattering.hip); the lag sweep's LDS is dynamic: 16 NC (256 + 63) bytes at most
   python tools/kernel_resources.py --sym OTHER_TREE every kernel of the units that see pair_blocks.h / sym_kernels.h (symmetric families, fp32
                                                     twins, one-sided sweeps): OTHER_TREE | this tree, resources and every pair loop, differing
                                                     rows marked and counted -- what a change to the shared pair arithmetic touched
@@ -95,6 +97,7 @@ def pair_loops(asm, mangled, floor=30):
 POTENTIAL_KERNELS = (("rmb_potential.hip", "potential_kernel"), ("rmb_sym.hip", "sym_force_kernel"))
 PAIR_HIST_KERNELS = (("rmb_pair_hist.hip", "pair_hist_kernel"), ("rmb_potential.hip", "potential_kernel"))
 MSD_KERNELS = (("rmb_msd.hip", "msd_"),)
+SCATTERING_KERNELS = (("rmb_scattering.hip", "scat_"),)
 MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
 
 
@@ -159,6 +162,9 @@ if __name__ == "__main__":
     sys.exit(0)
   if "--msd" in sys.argv:
     potential_table(isa_stats.ROOT, MSD_KERNELS)
+    sys.exit(0)
+  if "--scattering" in sys.argv:
+    potential_table(isa_stats.ROOT, SCATTERING_KERNELS)
     sys.exit(0)
   if "--pair-hist" in sys.argv:
     potential_table(isa_stats.ROOT, PAIR_HIST_KERNELS)
