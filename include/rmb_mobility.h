@@ -500,6 +500,33 @@ int rmb_scattering_lags_device(rmb_ctx* ctx, const double* modes_dev, long n_fra
                                double* sums_dev);
 int rmb_self_scattering_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, const int* kint,
                                       long K, long n_lags, long o_begin, long o_end, double* sums_dev);
+/* Lag histograms behind the van Hove correlation functions of point trajectories: the self part G_s(r, t), the distribution
+ * of single-point displacements, and the distinct part G_d(r, t), the time-dependent pair distribution (g(r) at t = 0).
+ * frames = (n_frames, n, 3) packed doubles on the device, possibly unwrapped; origins o in [o_begin, o_end), lags l in
+ * [0, n_lags), a pair (o, l) only where o + l < n_frames (the convention of rmb_msd_frames_device).  plane = 0: distances in
+ * three dimensions; 1: the z component of every separation and displacement is ignored.
+ *   rmb_van_hove_self_frames_device      hist[l, b] += #{(o, j) : bin(|x_j(o + l) - x_j(o)|) = b}, the displacement as it is
+ *                                        (no minimal image, as the MSD); moments[l] += (sum |D|^2, sum |D|^4) over ALL terms,
+ *                                        those at and beyond r_max included (NULL: not wanted).  A lane owns a point and keeps
+ *                                        x_j(o) over a tile of lags; per-workgroup partial moments, a finishing launch.
+ *   rmb_van_hove_distinct_frames_device  hist[l, b] += #{(o, i, j), i != j : bin(|image(x_i(o + l) - x_j(o))|) = b}: ORDERED
+ *                                        pairs, minimal image in every direction with L_d > 0 (L = 3 lengths on the host; valid
+ *                                        for separations of any number of periods).  A workgroup owns a lag; units (origin, tile,
+ *                                        tile) over the full tile grid, the 64-step rotation of the pair sweeps.  hist[0] summed
+ *                                        over origins is exactly twice rmb_pair_histogram_frames_device's counts.
+ * Binning is rmb_pair_histogram's: a term with r < r_max (compared as r^2 < r_max^2) lands in bin (int)(r n_bins / r_max), capped
+ * at n_bins - 1; r = 0 counts in bin 0; r >= r_max is dropped from the counts.  hist = (n_lags, n_bins) unsigned 64-bit, ADDED
+ * to: uint32 counters in LDS, integer atomics to the caller's bins, the same bits for every launch plan (a workgroup meets
+ * fewer than 2^31 terms, or the call is refused).  No floating-point atomics: the moments of the same call are the same bits.
+ * Normalisation is the caller's (vanhove.py).  Always fp64, single device, asynchronous on the context's stream.  Nothing of
+ * the resident configuration is read or written (only the context's device, stream and a workspace of the self entry).
+ * RMB_ERR_ARG, before the context or the device is touched: a null hist / frames / L pointer, negative sizes, n_lags < 1, not
+ * 0 <= o_begin <= o_end <= n_frames, plane not 0 or 1, r_max not positive and finite, n_bins outside 1 ... 8192, more pairs than
+ * one launch can step through.  n_frames = 0, o_begin = o_end, n = 0 and, for the distinct entry, n = 1 leave the outputs unchanged. */
+int rmb_van_hove_self_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, long n_lags, long o_begin, long o_end,
+                                    int plane, double r_max, long n_bins, unsigned long long* hist_dev, double* moments_dev_or_null);
+int rmb_van_hove_distinct_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, long n_lags,
+                                        long o_begin, long o_end, int plane, double r_max, long n_bins, unsigned long long* hist_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

@@ -86,6 +86,9 @@ SYMBOLS = {
     "rmb_density_modes_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp, ctypes.c_long, _vp]),
     "rmb_scattering_lags_device": (ctypes.c_int, [_vp, _vp] + [ctypes.c_long] * 5 + [_vp]),
     "rmb_self_scattering_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp] + [ctypes.c_long] * 4 + [_vp]),
+    "rmb_van_hove_self_frames_device": (ctypes.c_int, [_vp, _vp] + [ctypes.c_long] * 5 + [ctypes.c_int, ctypes.c_double, ctypes.c_long, _vp, _vp]),
+    "rmb_van_hove_distinct_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _vp] + [ctypes.c_long] * 3 +
+                                            [ctypes.c_int, ctypes.c_double, ctypes.c_long, _vp]),
     "rmb_mcmc_propose_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_double, _vp, _vp, _vp]),
     "rmb_mcmc_body_delta_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp] + [ctypes.c_double] * 6 +

@@ -23,6 +23,7 @@ def _ptr(x):
 
 
 POTENTIAL_FORMS = {"soft": 0, "yukawa": 1}   # rmb_blob_potential's `form`
+VAN_HOVE_PLANES = {"xyz": 0, "xy": 1}        # rmb_van_hove_*'s `plane`
 
 
 class MobilityContext(object):
@@ -697,6 +698,61 @@ class MobilityContext(object):
                                                            _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K, n_lags, int(o_begin),
                                                            int(o_end), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
     return out, counts
+
+  def _van_hove_args(self, frames, n_lags, r_max, n_bins, origins, plane, out, o_begin, o_end):
+    """Checks shared by the two van Hove entries -> (n_frames, n, n_lags, plane index, out, o_begin, o_end)."""
+    import torch
+    n_frames, n = self._scattering_frames(frames)
+    n_lags, n_bins = int(n_lags), int(n_bins)
+    from .msd import counts_per_lag
+    counts_per_lag(n_frames, 1, n_lags, origins)      # checks n_lags and origins
+    if plane not in VAN_HOVE_PLANES:
+      raise ValueError("plane must be one of %s, got %r" % (sorted(VAN_HOVE_PLANES), plane))
+    if out is None:
+      out = torch.zeros((n_lags, max(n_bins, 0)), dtype=torch.int64, device=frames.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and
+              tuple(out.shape) == (n_lags, n_bins)):
+      raise ValueError("out must be a contiguous CUDA int64 tensor of shape (n_lags, n_bins)")
+    if o_end is None:
+      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    return n_frames, n, n_lags, VAN_HOVE_PLANES[plane], out, int(o_begin), int(o_end)
+
+  def van_hove_self_frames_device(self, frames, n_lags, r_max, n_bins, origins="window", plane="xyz", out=None, moments=None, o_begin=0,
+                                  o_end=None):
+    """Counts behind the self part G_s(r, t) of the van Hove function of `frames`, a contiguous CUDA float64 tensor
+    (n_frames, n, 3), possibly unwrapped (rmb_van_hove_self_frames_device): hist[l, b] = number of (origin o, point j) whose
+    displacement |x_j(o + l) - x_j(o)| -- as it is, no minimal image -- falls in bin int(r n_bins / r_max), r < r_max; and
+    moments[l] = (sum r^2, sum r^4) over ALL terms, those beyond r_max included.  plane="xy" ignores the z component.
+    origins, o_begin and o_end as scattering_lags_device.  Both are ADDED to out= (contiguous CUDA int64 (n_lags, n_bins)) and
+    moments= (contiguous CUDA float64 (n_lags, 2)); None: new tensors of zeros.  Returns (hist, moments).  Asynchronous on
+    torch's stream; the resident configuration is neither read nor changed."""
+    import torch
+    n_frames, n, n_lags, pl, out, o_begin, o_end = self._van_hove_args(frames, n_lags, r_max, n_bins, origins, plane, out, o_begin, o_end)
+    if moments is None:
+      moments = torch.zeros((n_lags, 2), dtype=torch.float64, device=frames.device)
+    elif not (isinstance(moments, torch.Tensor) and moments.is_cuda and moments.dtype == torch.float64 and moments.is_contiguous() and
+              tuple(moments.shape) == (n_lags, 2)):
+      raise ValueError("moments must be a contiguous CUDA float64 tensor of shape (n_lags, 2)")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_van_hove_self_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
+                                                         n_lags, o_begin, o_end, pl, float(r_max), int(n_bins),
+                                                         ctypes.c_void_p(out.data_ptr()) if out.numel() else None,
+                                                         ctypes.c_void_p(moments.data_ptr())))
+    return out, moments
+
+  def van_hove_distinct_frames_device(self, frames, periodic_length, n_lags, r_max, n_bins, origins="window", plane="xyz", out=None, o_begin=0,
+                                      o_end=None):
+    """Counts behind the distinct part G_d(r, t): hist[l, b] = number of (origin o, ORDERED pair i != j) whose separation
+    x_i(o + l) - x_j(o), in the minimal image of every direction with a positive period (periodic_length: three periods, <= 0:
+    open), has its length in bin b (rmb_van_hove_distinct_frames_device).  Binning, plane, origins, o_begin, o_end and out= as
+    van_hove_self_frames_device; hist[0] summed over origins is twice pair_histogram_frames_device's counts.  Returns hist."""
+    n_frames, n, n_lags, pl, out, o_begin, o_end = self._van_hove_args(frames, n_lags, r_max, n_bins, origins, plane, out, o_begin, o_end)
+    L = _as_f64(periodic_length, 3)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_van_hove_distinct_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames,
+                                                             n, _ptr(L), n_lags, o_begin, o_end, pl, float(r_max), int(n_bins),
+                                                             ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
 
   @staticmethod
   def _body_law(body_potential):

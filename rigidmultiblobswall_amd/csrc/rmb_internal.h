@@ -32,6 +32,9 @@
 //                    sweep (a lane owns a lag), finishing launch
 //   rmb_scattering.hip  density modes rho_k(f) of caller-owned frames (scattering_kernels.h: a lane owns a wavevector) and the
 //                    lag sums of S(k), F(k, t), F_s(k, t) (a lane owns a lag, over the modes or per-point phase records)
+//   rmb_van_hove.hip  lag histograms behind the van Hove functions G_s(r, t), G_d(r, t) of caller-owned frames
+//                    (van_hove_kernels.h): self sweep (a lane owns a point; counts and the moments sum r^2, sum r^4, finishing
+//                    launch) and distinct sweep over ordered pairs (a workgroup owns a lag; the rotation of the pair-once frame)
 #pragma once
 #include "../../include/rmb_mobility.h"
 
@@ -93,6 +96,7 @@ struct CtxBuffers {
   DevBuf mcmc_ws;          // single-body moves (rmb_mcmc_moves.hip): per-wave partial differences + the proposed body
   DevBuf msd_ws;           // mean-square displacement (rmb_msd.hip): body-major records + per-workgroup partial sums
   DevBuf scat_ws;          // scattering (rmb_scattering.hip): n / L of the wavevectors, series-major records, partial sums
+  DevBuf vh_ws;            // van Hove self sweep (rmb_van_hove.hip): per-workgroup partial moments
   DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
   DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
   DevBuf krylov;   // partial sums of rmb_krylov_orthogonalize_device
@@ -102,7 +106,7 @@ struct CtxBuffers {
 using CB = CtxBuffers;
 constexpr DevBuf CB::* kCtxBufs[] = {&CB::pos, &CB::r_stage, &CB::vec, &CB::vec2, &CB::out, &CB::partial, &CB::tmp3n, &CB::tile_bounds,
                                      &CB::fpos, &CB::fperm, &CB::fsort_keys, &CB::fsort_vals, &CB::fsort_tmp, &CB::fsort_box,
-                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
+                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::vh_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
 static_assert(sizeof(CtxBuffers) == (sizeof(kCtxBufs) / sizeof(kCtxBufs[0]) + 8) * sizeof(DevBuf),
               "a DevBuf of CtxBuffers is missing from kCtxBufs (or st[] changed its length)");
 template <class Bufs, class F>      // Bufs: CtxBuffers or const CtxBuffers (an rmb_ctx converts)
