@@ -164,8 +164,10 @@ template <bool PERIODIC, bool RADII> struct ForceOp {
       // far: -(eps/b) exp(-(r-2a)/b)/r ; near (r <= 2a): -(eps/b)/max(r,1e-25) = -(eps/b) min(1/r, 1e25)
       const double two_a = RADII ? tg.ra + q1.y : a.two_a;
       // branch-free (sym_force_kernels.h pair_force): x = 0 exactly for r <= 2a, exp(0) = 1, min(1/r, 1e25) = 1/r beyond
+      // (eps/b) min(1/r, 1e25) first, the exponential last: e is a denormal beyond (r - 2a)/b = 708 and e / r would be
+      // rounded to the denormal grid BEFORE it is scaled up by eps/b (sym_force_kernels.h, BlobContactLaw)
       const double e = exp_nonpositive(a.ec, fmin((two_a - r) * a.inv_b, 0.0));
-      double f0 = -a.eps_over_b * (e * fmin(ir, 1e25));
+      double f0 = -((a.eps_over_b * fmin(ir, 1e25)) * e);
       if (j0 + s == ti) f0 = 0.0;  // i == j (r2 = 0 -> ir = inf; select, do not multiply)
       if (j0 + s == ti) { dx = 0.0; dy = 0.0; dz = 0.0; }
       fx = __builtin_fma(f0, dx, fx); fy = __builtin_fma(f0, dy, fy); fz = __builtin_fma(f0, dz, fz);

@@ -47,7 +47,9 @@ struct BlobContactLaw {
   static __device__ __forceinline__ double f0(const SymForceArgs& a, double two_a, double r, double ir) {
     const double x = fmin((two_a - r) * a.inv_b, 0.0);
     const double e = exp_nonpositive(a.ec, x);
-    return -a.eps_over_b * (e * fmin(ir, 1e25));
+    // the multiplier first, the exponential last: beyond (r - 2a)/b = 708 e is a denormal, and e min(1/r, 1e25) would be
+    // rounded to the denormal grid before eps/b scales it up again -- r times the error of one rounding of the result
+    return -((a.eps_over_b * fmin(ir, 1e25)) * e);
   }
 };
 
@@ -59,7 +61,7 @@ struct BlobContactLaw {
 struct BodyYukawaLaw {
   static __device__ __forceinline__ double f0(const SymForceArgs& a, double, double r, double ir) {
     const double e = exp_nonpositive(a.ec, fmin(-r * a.inv_b, 0.0));
-    return -__builtin_fma(a.eps, ir, a.eps_over_b) * (e * (ir * ir));
+    return -((__builtin_fma(a.eps, ir, a.eps_over_b) * (ir * ir)) * e);      // the denormal e last, as above
   }
 };
 
