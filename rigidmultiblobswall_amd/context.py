@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._lagged import counts_per_lag
 
 
 def _as_f64(x, n3=None):
@@ -20,6 +21,27 @@ def _as_f64(x, n3=None):
 
 def _ptr(x):
   return ctypes.c_void_p(x.ctypes.data)
+
+
+def _lag_origins(n_frames, n_series, n_lags, origins, o_begin=0, o_end=None):
+  """(counts, o_begin, o_end) of a lag entry: counts is counts_per_lag (which checks n_lags and origins) of the whole range;
+  o_end=None is the last origin of the convention `origins`."""
+  counts = counts_per_lag(n_frames, n_series, n_lags, origins)
+  if o_end is None:
+    o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+  return counts, int(o_begin), int(o_end)
+
+
+def _cuda_out(out, shape, named, dtype, device, what="out", zero=True):
+  """The out= rules of the entries whose result has a shape: a contiguous CUDA tensor of dtype `dtype` ("float64", "int64") and
+  shape `shape` (`named` in the refusal); None makes one, of zeros where the entry ADDS to it."""
+  import torch
+  if out is None:
+    return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, dtype), device=device)
+  if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == getattr(torch, dtype) and out.is_contiguous() and
+          tuple(out.shape) == tuple(shape)):
+    raise ValueError("%s must be a contiguous CUDA %s tensor of shape %s" % (what, dtype, named))
+  return out
 
 
 POTENTIAL_FORMS = {"soft": 0, "yukawa": 1}   # rmb_blob_potential's `form`
@@ -594,19 +616,13 @@ class MobilityContext(object):
     if not _is_torch_cuda(frames) or frames.dtype != torch.float64 or not frames.is_contiguous() or frames.dim() != 3 or frames.shape[-1] != 7:
       raise ValueError("frames must be a contiguous CUDA float64 tensor of shape (n_frames, n_bodies, 7)")
     n_frames, n_bodies, n_lags = int(frames.shape[0]), int(frames.shape[1]), int(n_lags)
-    from .msd import counts_per_lag
-    counts = counts_per_lag(n_frames, n_bodies, n_lags, origins)      # checks n_lags and origins
+    counts, _, o_end = _lag_origins(n_frames, n_bodies, n_lags, origins)
     if offsets is not None:
       if not isinstance(offsets, torch.Tensor):
         offsets = torch.from_numpy(_as_f64(offsets, 3 * n_bodies)).to(frames.device)
       if not (offsets.is_cuda and offsets.dtype == torch.float64 and offsets.is_contiguous() and offsets.numel() == 3 * n_bodies):
         raise ValueError("offsets must hold (n_bodies, 3) float64 values")
-    if out is None:
-      out = torch.zeros((n_lags, 6, 6), dtype=torch.float64, device=frames.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-              tuple(out.shape) == (n_lags, 6, 6)):
-      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_lags, 6, 6)")
-    o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    out = _cuda_out(out, (n_lags, 6, 6), "(n_lags, 6, 6)", "float64", frames.device)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_msd_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n_bodies,
                                                ctypes.c_void_p(offsets.data_ptr()) if offsets is not None and offsets.numel() else None,
@@ -628,30 +644,16 @@ class MobilityContext(object):
       raise ValueError("wavevectors must be an integer array of shape (K, 3)")
     return L, np.ascontiguousarray(np.clip(k, -2 ** 30, 2 ** 30), dtype=np.int32)      # beyond int32: still beyond what the entry accepts
 
-  @staticmethod
-  def _scattering_out(out, n_lags, K, device):
-    import torch
-    if out is None:
-      return torch.zeros((n_lags, K), dtype=torch.float64, device=device)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n_lags, K)):
-      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_lags, K)")
-    return out
-
   def density_modes_frames_device(self, frames, periodic_length, wavevectors, out=None):
     """Density modes rho_k(f) = sum_j exp(-i k . x_j(f)) of `frames`, a contiguous CUDA float64 tensor (n_frames, n, 3)
     (rmb_density_modes_frames_device).  wavevectors: integer array (K, 3) of n, k = 2 pi n_d / L_d; periodic_length: the three
     L_d (a period, or any reference length of an open direction; <= 0 only where every n_d = 0).  Returns a CUDA float64 tensor
     (n_frames, K, 2) of (Re, Im) = (sum cos, -sum sin); out= (that shape, contiguous) is OVERWRITTEN.  Asynchronous on torch's
     stream; the resident configuration is neither read nor changed."""
-    import torch
     n_frames, n = self._scattering_frames(frames)
     L, k = self._scattering_wavevectors(periodic_length, wavevectors)
     K = int(k.shape[0])
-    if out is None:
-      out = torch.empty((n_frames, K, 2), dtype=torch.float64, device=frames.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-              tuple(out.shape) == (n_frames, K, 2)):
-      raise ValueError("out must be a contiguous CUDA float64 tensor of shape (n_frames, K, 2)")
+    out = _cuda_out(out, (n_frames, K, 2), "(n_frames, K, 2)", "float64", frames.device, zero=False)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_density_modes_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
                                                          _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K,
@@ -669,14 +671,11 @@ class MobilityContext(object):
     if not _is_torch_cuda(modes) or modes.dtype != torch.float64 or not modes.is_contiguous() or modes.dim() != 3 or modes.shape[-1] != 2:
       raise ValueError("modes must be a contiguous CUDA float64 tensor of shape (n_frames, K, 2)")
     n_frames, K, n_lags = int(modes.shape[0]), int(modes.shape[1]), int(n_lags)
-    from .msd import counts_per_lag
-    counts = counts_per_lag(n_frames, 1, n_lags, origins)      # checks n_lags and origins
-    out = self._scattering_out(out, n_lags, K, modes.device)
-    if o_end is None:
-      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    counts, o_begin, o_end = _lag_origins(n_frames, 1, n_lags, origins, o_begin, o_end)
+    out = _cuda_out(out, (n_lags, K), "(n_lags, K)", "float64", modes.device)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_scattering_lags_device(self._h, ctypes.c_void_p(modes.data_ptr()) if modes.numel() else None, n_frames, K, n_lags,
-                                                    int(o_begin), int(o_end), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+                                                    o_begin, o_end, ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
     return out, counts
 
   def self_scattering_frames_device(self, frames, periodic_length, wavevectors, n_lags, origins="window", out=None, o_begin=0, o_end=None):
@@ -688,34 +687,23 @@ class MobilityContext(object):
     n_frames, n = self._scattering_frames(frames)
     L, k = self._scattering_wavevectors(periodic_length, wavevectors)
     K, n_lags = int(k.shape[0]), int(n_lags)
-    from .msd import counts_per_lag
-    counts = counts_per_lag(n_frames, 1, n_lags, origins)
-    out = self._scattering_out(out, n_lags, K, frames.device)
-    if o_end is None:
-      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
+    counts, o_begin, o_end = _lag_origins(n_frames, 1, n_lags, origins, o_begin, o_end)
+    out = _cuda_out(out, (n_lags, K), "(n_lags, K)", "float64", frames.device)
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_self_scattering_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
-                                                           _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K, n_lags, int(o_begin),
-                                                           int(o_end), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+                                                           _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None, K, n_lags, o_begin,
+                                                           o_end, ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
     return out, counts
 
   def _van_hove_args(self, frames, n_lags, r_max, n_bins, origins, plane, out, o_begin, o_end):
     """Checks shared by the two van Hove entries -> (n_frames, n, n_lags, plane index, out, o_begin, o_end)."""
-    import torch
     n_frames, n = self._scattering_frames(frames)
     n_lags, n_bins = int(n_lags), int(n_bins)
-    from .msd import counts_per_lag
-    counts_per_lag(n_frames, 1, n_lags, origins)      # checks n_lags and origins
+    _, o_begin, o_end = _lag_origins(n_frames, 1, n_lags, origins, o_begin, o_end)
     if plane not in VAN_HOVE_PLANES:
       raise ValueError("plane must be one of %s, got %r" % (sorted(VAN_HOVE_PLANES), plane))
-    if out is None:
-      out = torch.zeros((n_lags, max(n_bins, 0)), dtype=torch.int64, device=frames.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and
-              tuple(out.shape) == (n_lags, n_bins)):
-      raise ValueError("out must be a contiguous CUDA int64 tensor of shape (n_lags, n_bins)")
-    if o_end is None:
-      o_end = max(n_frames - n_lags + 1, 0) if origins == "window" else n_frames
-    return n_frames, n, n_lags, VAN_HOVE_PLANES[plane], out, int(o_begin), int(o_end)
+    out = _cuda_out(out, (n_lags, max(n_bins, 0)), "(n_lags, n_bins)", "int64", frames.device)
+    return n_frames, n, n_lags, VAN_HOVE_PLANES[plane], out, o_begin, o_end
 
   def van_hove_self_frames_device(self, frames, n_lags, r_max, n_bins, origins="window", plane="xyz", out=None, moments=None, o_begin=0,
                                   o_end=None):
@@ -726,13 +714,8 @@ class MobilityContext(object):
     origins, o_begin and o_end as scattering_lags_device.  Both are ADDED to out= (contiguous CUDA int64 (n_lags, n_bins)) and
     moments= (contiguous CUDA float64 (n_lags, 2)); None: new tensors of zeros.  Returns (hist, moments).  Asynchronous on
     torch's stream; the resident configuration is neither read nor changed."""
-    import torch
     n_frames, n, n_lags, pl, out, o_begin, o_end = self._van_hove_args(frames, n_lags, r_max, n_bins, origins, plane, out, o_begin, o_end)
-    if moments is None:
-      moments = torch.zeros((n_lags, 2), dtype=torch.float64, device=frames.device)
-    elif not (isinstance(moments, torch.Tensor) and moments.is_cuda and moments.dtype == torch.float64 and moments.is_contiguous() and
-              tuple(moments.shape) == (n_lags, 2)):
-      raise ValueError("moments must be a contiguous CUDA float64 tensor of shape (n_lags, 2)")
+    moments = _cuda_out(moments, (n_lags, 2), "(n_lags, 2)", "float64", frames.device, what="moments")
     self._follow_torch_stream()
     _lib.check(self._lib.rmb_van_hove_self_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
                                                          n_lags, o_begin, o_end, pl, float(r_max), int(n_bins),

@@ -57,9 +57,10 @@ def format_gr(r, g, counts):
   return "".join("%g %g %d\n" % (ri, gi, 2 * int(ci)) for ri, gi, ci in zip(r, g, counts))
 
 
-def read_frames(path_or_paths, n_points):
+def read_frames(path_or_paths, n_points, columns=3):
   """Frames of a trajectory as (n_frames, n_points, 3): a `.config` file (one count line, then `x y z q0 q1 q2 q3` per body,
-  repeated for every saved step; a final newline or none), or a list of such files -- e.g. one `.clones` file per step."""
+  repeated for every saved step; a final newline or none), or a list of such files -- e.g. one `.clones` file per step.
+  columns=7 keeps the quaternions too."""
   paths = [path_or_paths] if isinstance(path_or_paths, (str, bytes)) or hasattr(path_or_paths, "__fspath__") else list(path_or_paths)
   n_points = int(n_points)
   if n_points < 0:
@@ -74,15 +75,15 @@ def read_frames(path_or_paths, n_points):
     tok = tok.reshape(-1, block)
     if tok.size and np.any(tok[:, 0] != n_points):
       raise ValueError("%s: a frame announces %d bodies, expected %d" % (path, int(tok[tok[:, 0] != n_points][0, 0]), n_points))
-    out.append(tok[:, 1:].reshape(-1, n_points, 7)[:, :, :3])
-  return np.ascontiguousarray(np.concatenate(out)) if out else np.zeros((0, n_points, 3))
+    out.append(tok[:, 1:].reshape(-1, n_points, 7)[:, :, :columns])
+  return np.ascontiguousarray(np.concatenate(out)) if out else np.zeros((0, n_points, columns))
 
 
-def load_trajectory(path_or_paths, n_points, skip=0):
+def load_trajectory(path_or_paths, n_points, skip=0, columns=3):
   """read_frames without the first `skip` frames (the reference program's `skip`: they are neither counted nor normalised by)."""
   if int(skip) < 0:
     raise ValueError("skip must not be negative, got %r" % (skip,))
-  frames = read_frames(path_or_paths, n_points)[int(skip):]
+  frames = read_frames(path_or_paths, n_points, columns)[int(skip):]
   if frames.shape[0] < 1:
     raise ValueError("no frame left after skipping %d" % int(skip))
   return frames

@@ -28,13 +28,16 @@
 //                    in LDS, integer atomics to the caller's uint64 bins): resident points, and a batch of caller-owned frames
 //   rmb_laplace.hip  Laplace layer operators of phoretic bodies (laplace_kernels.h): the six reference-shaped host entry
 //                    points and the two fused device sweeps of the concentration solve
-//   rmb_msd.hip      6 x 6 mean-square displacement sums of caller-owned rigid-body frames (msd_kernels.h): record pass, lag
-//                    sweep (a lane owns a lag), finishing launch
+//   rmb_msd.hip      6 x 6 mean-square displacement sums of caller-owned rigid-body frames (msd_kernels.h: a policy of the
+//                    lag-sweep frame, lag_sweep_kernels.h -- a lane owns a lag): record pass, lag sweep, finishing launch
 //   rmb_scattering.hip  density modes rho_k(f) of caller-owned frames (scattering_kernels.h: a lane owns a wavevector) and the
-//                    lag sums of S(k), F(k, t), F_s(k, t) (a lane owns a lag, over the modes or per-point phase records)
+//                    lag sums of S(k), F(k, t), F_s(k, t) (the other policy of that frame, over the modes or per-point phase
+//                    records)
 //   rmb_van_hove.hip  lag histograms behind the van Hove functions G_s(r, t), G_d(r, t) of caller-owned frames
 //                    (van_hove_kernels.h): self sweep (a lane owns a point; counts and the moments sum r^2, sum r^4, finishing
 //                    launch) and distinct sweep over ordered pairs (a workgroup owns a lag; the rotation of the pair-once frame)
+//   lag_sweep_host.h (a header, included by the three units above) the checks of a batch of frames and of a lag / origin
+//                    range, pad256, and the one launch plan of the lag sweeps (plan_lag_sweep)
 #pragma once
 #include "../../include/rmb_mobility.h"
 

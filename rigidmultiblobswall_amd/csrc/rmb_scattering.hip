@@ -2,16 +2,13 @@
 // the intermediate scattering function F(k, t) and its self part F_s(k, t) (scattering_kernels.h): the modes sweep (a lane
 // owns a wavevector), the lag sweep (a lane owns a lag) over the modes or over per-point phase records, and their finishing
 // launches; what scattering.py is built on.
-#include "rmb_internal.h"
-
+#include "lag_sweep_host.h"
 #include "scattering_kernels.h"
 
 namespace rmbi {
 namespace {
 
 constexpr long kScatMaxK = 16384, kScatMaxN = 32768;
-
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int check_wavevectors(const char* who, const double* L, const int* kint, long K) {
   const std::string w(who);
@@ -24,14 +21,6 @@ int check_wavevectors(const char* who, const double* L, const int* kint, long K)
     if (n > kScatMaxN || n < -kScatMaxN) return fail(RMB_ERR_ARG, w + ": |n_d| must be at most 32768");
     if (n != 0 && !(L[i % 3] > 0.0)) return fail(RMB_ERR_ARG, w + ": n_d != 0 needs a positive length L_d");
   }
-  return 0;
-}
-
-int check_lags(const char* who, long n_frames, long n_lags, long o_begin, long o_end) {
-  const std::string w(who);
-  if (n_lags < 1) return fail(RMB_ERR_ARG, w + ": n_lags must be at least 1");
-  if (n_lags > (1L << 24)) return fail(RMB_ERR_ARG, w + ": n_lags must be at most 2^24");
-  if (o_begin < 0 || o_end < o_begin || o_end > n_frames) return fail(RMB_ERR_ARG, w + ": origins must satisfy 0 <= o_begin <= o_end <= n_frames");
   return 0;
 }
 
@@ -79,29 +68,10 @@ int modes_impl(rmb_ctx* c, const double* frames_dev, long n_frames, long n, cons
   return 0;
 }
 
-// Launch plan of a lag sweep over `rows` rows of `series` series each: about eight workgroups per CU over all rows and lag
-// blocks (more only add partials), never more than a row has work items.  Fills everything of `a` but rec / part / sums.
-int plan_sweep(rmb_ctx* c, rmb::ScatSweepArgs& a, long n_frames, long series, long rows, long n_lags, long o_begin, long o_end) {
-  a.F = n_frames; a.B = series;
-  a.n_lags = n_lags; a.lag_blocks = (n_lags + 63) / 64;
-  a.o_begin = o_begin; a.o_end = o_end;
-  const long n_origins = o_end - o_begin;
-  a.chunk = rmb::kScatChunk < n_origins ? rmb::kScatChunk : n_origins;
-  a.n_chunks = (n_origins + a.chunk - 1) / a.chunk;
-  if ((double)a.n_chunks * (double)series > 1.0e15) return fail(RMB_ERR_ARG, "scattering: too many work items for one call");
-  a.items = a.n_chunks * series;
-  const long per = a.lag_blocks * rows, target = 8 * c->n_cu;
-  a.P = (target + per - 1) / per;
-  if (a.P > a.items) a.P = a.items;
-  if ((double)a.items * (double)(a.P + 1) > 9.0e18) return fail(RMB_ERR_ARG, "scattering: too many work items for one call");
-  if (a.P * a.lag_blocks > 0x7fffffffL) return fail(RMB_ERR_ARG, "scattering: too many lag blocks for one launch");
-  return 0;
-}
-
 template <int NC>
 int launch_sweep(rmb_ctx* c, const rmb::ScatSweepArgs& a, long rows) {
-  hipLaunchKernelGGL(rmb::scat_sweep_kernel<NC>, dim3((unsigned)(a.P * a.lag_blocks), (unsigned)rows), dim3(rmb::kScatBlock),
-                     rmb::scat_sweep_lds(a.chunk, NC), c->stream, a);
+  hipLaunchKernelGGL(rmb::scat_sweep_kernel<NC>, dim3((unsigned)(a.P * a.lag_blocks), (unsigned)rows), dim3(rmb::kLagBlock),
+                     rmb::lag_sweep_lds(a.chunk, rmb::ScatOp<NC>::R, rmb::ScatOp<NC>::NS), c->stream, a);
   RMB_HIP(hipGetLastError());
   hipLaunchKernelGGL(rmb::scat_sweep_finish_kernel<NC>, dim3((unsigned)((a.n_lags * a.k_count + 255) / 256)), dim3(256), 0, c->stream, a);
   RMB_HIP(hipGetLastError());
@@ -111,7 +81,7 @@ int launch_sweep(rmb_ctx* c, const rmb::ScatSweepArgs& a, long rows) {
 int lags_impl(rmb_ctx* c, const double* modes_dev, long n_frames, long K, long n_lags, long o_begin, long o_end, double* sums_dev) {
   if (n_frames == 0 || K == 0 || o_begin == o_end) return 0;
   rmb::ScatSweepArgs a{};
-  if (int rc = plan_sweep(c, a, n_frames, 1, K, n_lags, o_begin, o_end)) return rc;
+  if (int rc = plan_lag_sweep(c, a, "scattering", n_frames, 1, K, n_lags, o_begin, o_end, rmb::kScatChunk)) return rc;
   a.sums = sums_dev; a.K = K; a.k0 = 0; a.k_count = K;
   const size_t rec_bytes = pad256((size_t)n_frames * K * 2 * sizeof(double));
   const size_t part_bytes = (size_t)K * a.P * a.lag_blocks * 64 * sizeof(double);
@@ -132,7 +102,7 @@ int self_impl(rmb_ctx* c, const double* frames_dev, long n_frames, long n, const
               long o_end, double* sums_dev) {
   if (n_frames == 0 || K == 0 || n == 0 || o_begin == o_end) return 0;
   rmb::ScatSweepArgs a{};
-  if (int rc = plan_sweep(c, a, n_frames, n, 1, n_lags, o_begin, o_end)) return rc;
+  if (int rc = plan_lag_sweep(c, a, "scattering", n_frames, n, 1, n_lags, o_begin, o_end, rmb::kScatChunk)) return rc;
   a.sums = sums_dev; a.K = K;
   const long pairs = n_frames * n;
   if ((pairs + 255) / 256 > 0x7fffffffL) return fail(RMB_ERR_ARG, "self scattering: too many frames for one launch");
@@ -183,10 +153,8 @@ extern "C" {
 
 int rmb_density_modes_frames_device(rmb_ctx* c, const double* frames_dev, long n_frames, long n, const double* L, const int* kint, long K,
                                     double* modes_dev) {
-  if (n_frames < 0 || n < 0) return fail(RMB_ERR_ARG, "density modes: negative size");
+  if (int rc = rmbi::check_frames("density modes", frames_dev, n_frames, n, 3)) return rc;
   if (int rc = rmbi::check_wavevectors("density modes", L, kint, K)) return rc;
-  if ((double)n_frames * (double)n * 3.0 > 1.0e18) return fail(RMB_ERR_ARG, "density modes: too many frames for one call");
-  if (n_frames > 0 && n > 0 && !frames_dev) return fail(RMB_ERR_ARG, "density modes: null frames pointer");
   if (n_frames > 0 && K > 0 && !modes_dev) return fail(RMB_ERR_ARG, "density modes: null modes pointer");
   if (!c) return fail(RMB_ERR_ARG, "null context");      // last: the argument checks need no context, let alone a device
   return rmbi::modes_impl(c, frames_dev, n_frames, n, L, kint, K, modes_dev);
@@ -194,11 +162,9 @@ int rmb_density_modes_frames_device(rmb_ctx* c, const double* frames_dev, long n
 
 int rmb_scattering_lags_device(rmb_ctx* c, const double* modes_dev, long n_frames, long K, long n_lags, long o_begin, long o_end,
                                double* sums_dev) {
-  if (n_frames < 0 || K < 0) return fail(RMB_ERR_ARG, "scattering lags: negative size");
+  if (int rc = rmbi::check_frames("scattering lags", modes_dev, n_frames, K, 2, "modes")) return rc;
   if (K > rmbi::kScatMaxK) return fail(RMB_ERR_ARG, "scattering lags: at most 16384 wavevectors per call");
-  if (int rc = rmbi::check_lags("scattering lags", n_frames, n_lags, o_begin, o_end)) return rc;
-  if ((double)n_frames * (double)K * 2.0 > 1.0e18) return fail(RMB_ERR_ARG, "scattering lags: too many frames for one call");
-  if (n_frames > 0 && K > 0 && !modes_dev) return fail(RMB_ERR_ARG, "scattering lags: null modes pointer");
+  if (int rc = rmbi::check_lag_range("scattering lags", n_frames, n_lags, o_begin, o_end)) return rc;
   if (K > 0 && !sums_dev) return fail(RMB_ERR_ARG, "scattering lags: null sums pointer");
   if (!c) return fail(RMB_ERR_ARG, "null context");
   return rmbi::lags_impl(c, modes_dev, n_frames, K, n_lags, o_begin, o_end, sums_dev);
@@ -206,11 +172,9 @@ int rmb_scattering_lags_device(rmb_ctx* c, const double* modes_dev, long n_frame
 
 int rmb_self_scattering_frames_device(rmb_ctx* c, const double* frames_dev, long n_frames, long n, const double* L, const int* kint, long K,
                                       long n_lags, long o_begin, long o_end, double* sums_dev) {
-  if (n_frames < 0 || n < 0) return fail(RMB_ERR_ARG, "self scattering: negative size");
+  if (int rc = rmbi::check_frames("self scattering", frames_dev, n_frames, n, 2 * rmb::kScatGroup)) return rc;      // the records' width
   if (int rc = rmbi::check_wavevectors("self scattering", L, kint, K)) return rc;
-  if (int rc = rmbi::check_lags("self scattering", n_frames, n_lags, o_begin, o_end)) return rc;
-  if ((double)n_frames * (double)n * 6.0 > 1.0e18) return fail(RMB_ERR_ARG, "self scattering: too many frames for one call");
-  if (n_frames > 0 && n > 0 && !frames_dev) return fail(RMB_ERR_ARG, "self scattering: null frames pointer");
+  if (int rc = rmbi::check_lag_range("self scattering", n_frames, n_lags, o_begin, o_end)) return rc;
   if (K > 0 && !sums_dev) return fail(RMB_ERR_ARG, "self scattering: null sums pointer");
   if (!c) return fail(RMB_ERR_ARG, "null context");
   return rmbi::self_impl(c, frames_dev, n_frames, n, L, kint, K, n_lags, o_begin, o_end, sums_dev);

@@ -1,6 +1,6 @@
 // rmb_van_hove.hip -- lag histograms behind the van Hove functions G_s(r, t) and G_d(r, t) of caller-owned point frames
 // (van_hove_kernels.h): the self sweep with its moments and finishing launch, and the distinct sweep over ordered pairs.
-#include "rmb_internal.h"
+#include "lag_sweep_host.h"
 
 #include <cmath>
 
@@ -16,15 +16,11 @@ int check_van_hove_args(const char* who, const void* frames, long n_frames, long
                         double r_max, long n_bins, const void* hist) {
   const std::string w(who);
   if (!hist) return fail(RMB_ERR_ARG, w + ": null histogram pointer");
-  if (n_frames < 0 || n < 0) return fail(RMB_ERR_ARG, w + ": negative size");
-  if (n_lags < 1) return fail(RMB_ERR_ARG, w + ": n_lags must be at least 1");
-  if (n_lags > (1L << 24)) return fail(RMB_ERR_ARG, w + ": n_lags must be at most 2^24");
-  if (o_begin < 0 || o_end < o_begin || o_end > n_frames) return fail(RMB_ERR_ARG, w + ": origins must satisfy 0 <= o_begin <= o_end <= n_frames");
+  if (int rc = check_frames(who, frames, n_frames, n, 3)) return rc;
+  if (int rc = check_lag_range(who, n_frames, n_lags, o_begin, o_end)) return rc;
   if (plane != 0 && plane != 1) return fail(RMB_ERR_ARG, w + ": plane must be 0 (xyz) or 1 (xy)");
   if (!(r_max > 0.0) || !std::isfinite(r_max)) return fail(RMB_ERR_ARG, w + ": r_max must be positive and finite");
   if (n_bins < 1 || n_bins > rmb::kPairHistMaxBins) return fail(RMB_ERR_ARG, w + ": n_bins must be 1 ... 8192");
-  if ((double)n_frames * (double)n * 3.0 > 1.0e18) return fail(RMB_ERR_ARG, w + ": too many frames for one call");
-  if (n_frames > 0 && n > 0 && !frames) return fail(RMB_ERR_ARG, w + ": null frames pointer");
   return 0;
 }
 

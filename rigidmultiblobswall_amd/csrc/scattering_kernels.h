@@ -24,16 +24,15 @@
 //   scat_transpose_kernel / scat_record_kernel   the records of the lag sweep, series-major and time-contiguous: the modes
 //                       of a wavevector (F, K, 2) -> (K, F, 2), or the phases z_jk(f) of a group of NC <= 3 wavevectors
 //                       (N, F, 2 NC), computed once per (frame, point), not once per pair.
-//   scat_sweep_kernel   a LANE OWNS A LAG, as msd_sweep_kernel: a workgroup serves one block of 64 lags and a range of work
-//                       items (series, origin chunk) of row blockIdx.y; the lagged records are a sliding window staged in
-//                       LDS component-major (lane l reads win[c][o - o0 + l]: 64 consecutive doubles, conflict-free
-//                       ds_read_b64), the origin record is wave-uniform, NC sums per lane in registers.  Frames past the
-//                       end are staged as zeros and add exactly nothing -- no mask.  Partials per workgroup.
+//   scat_sweep_kernel   a LANE OWNS A LAG: the frame of lag_sweep_kernels.h (schedule, staging, order of additions) with
+//                       ScatOp<NC> -- records of 2 NC doubles, NC sums per lane in registers, one row per wavevector
+//                       (collective) or one row of N points (self).  Frames past the end are staged as zeros and add
+//                       exactly nothing -- no mask.
 //   scat_sweep_finish_kernel  adds the partials of a (lag, wavevector) in block order INTO the caller's (n_lags, K).
 //
 // No floating-point atomic anywhere: the same call gives the same bits.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "lag_sweep_kernels.h"
 
 namespace rmb {
 
@@ -67,14 +66,7 @@ struct ScatRecordArgs {
   double c[3 * kScatGroup];  // c_d of the group's wavevectors (record kernel)
 };
 
-struct ScatSweepArgs {
-  const double* rec;       // [Y][B][F][2 NC]
-  long F, B;               // frames, series per row (points; 1 for the collective sums)
-  long n_lags, lag_blocks;
-  long o_begin, o_end;
-  long chunk, n_chunks;    // origins per work item, work items per series
-  long items, P;           // B * n_chunks work items over P workgroups per lag block
-  double* part;            // [Y][P * lag_blocks][NC][64]
+struct ScatSweepArgs : LagSweepArgs {      // B: points; 1 for the collective sums
   double* sums;            // (n_lags, K), added to
   long K, k0, k_count;     // row y, component c is wavevector k0 + y NC + c; k_count of them in all
 };
@@ -185,64 +177,27 @@ __global__ __launch_bounds__(256) void scat_record_kernel(const ScatRecordArgs a
   }
 }
 
-inline size_t scat_sweep_lds(long chunk, int nc) {
-  const size_t win = (size_t)(chunk + 63) * 2 * nc * sizeof(double), slab = (size_t)nc * 64 * sizeof(double);
-  return win > slab ? win : slab;
-}
+// The policy of the frame: records of the phases (or modes) of NC wavevectors, one sum each.
+template <int NC>
+struct ScatOp {
+  typedef ScatSweepArgs Args;
+  static constexpr int R = 2 * NC, NS = NC;
+  static constexpr bool MASK_TAIL = false;      // a zero record adds exactly nothing
+  template <bool MASKED>
+  static __device__ __forceinline__ void pair(double (&acc)[NC], const double* win, int W, int j, const double* org, bool) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      // Re(b conj a): one rounded product, one fused step, one addition to the sum
+      const double t = __builtin_fma(win[2 * c * W + j], org[2 * c], win[(2 * c + 1) * W + j] * org[2 * c + 1]);
+      acc[c] += t;
+    }
+  }
+};
 
 template <int NC>
-__global__ __launch_bounds__(kScatBlock) void scat_sweep_kernel(const ScatSweepArgs a) {
-  extern __shared__ double scat_lds[];      // win[2 NC][W], W = chunk + 63; later the combine slab [NC][64]
-  constexpr int R = 2 * NC;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long lb = blockIdx.x % a.lag_blocks, p = blockIdx.x / a.lag_blocks;
-  const long l0 = 64 * lb;
-  const long W = a.chunk + 63;
-  const int Wi = (int)W;
-  const long item_begin = a.items * p / a.P, item_end = a.items * (p + 1) / a.P;
-  const double* row = a.rec + (size_t)blockIdx.y * a.B * a.F * R;
-
-  double acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-
-  for (long item = item_begin; item < item_end; ++item) {
-    const long b = item / a.n_chunks, ch = item - b * a.n_chunks;
-    const long o0 = a.o_begin + ch * a.chunk;
-    const long o1 = o0 + a.chunk < a.o_end ? o0 + a.chunk : a.o_end;
-    const double* series = row + R * b * a.F;
-    // stage records f0 .. f0 + W - 1 (zeros past the last frame): a contiguous run of the series
-    const long f0 = o0 + l0;
-    const long have = f0 < a.F ? (a.F - f0 < W ? a.F - f0 : W) : 0;
-    __syncthreads();      // the previous item's readers are done
-    for (long i = threadIdx.x; i < R * W; i += kScatBlock) {
-      const long j = i / R, c = i - R * j;
-      scat_lds[c * W + j] = j < have ? series[R * f0 + i] : 0.0;
-    }
-    __syncthreads();
-    for (long o = o0 + wave; o < o1; o += kScatWaves) {
-      const double* org = series + R * o;      // wave-uniform
-      const int j = (int)(o - o0) + lane;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        // Re(b conj a): one rounded product, one fused step, one addition to the sum
-        const double t = __builtin_fma(scat_lds[2 * c * Wi + j], org[2 * c], scat_lds[(2 * c + 1) * Wi + j] * org[2 * c + 1]);
-        acc[c] += t;
-      }
-    }
-  }
-
-  for (int w = 0; w < kScatWaves; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) scat_lds[c * 64 + lane] = w == 0 ? acc[c] : scat_lds[c * 64 + lane] + acc[c];
-    }
-  }
-  __syncthreads();
-  double* out = a.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (NC * 64);
-  for (int i = threadIdx.x; i < NC * 64; i += kScatBlock) out[i] = scat_lds[i];
+__global__ __launch_bounds__(kLagBlock) void scat_sweep_kernel(const ScatSweepArgs a) {
+  extern __shared__ double scat_lds[];      // the frame's window win[2 NC][W], later its combine slab [NC][64]
+  lag_sweep<ScatOp<NC>>(a, scat_lds);
 }
 
 // one thread per (lag, wavevector of this launch): the partials of the P workgroups of its lag block in block order
@@ -252,13 +207,7 @@ __global__ __launch_bounds__(256) void scat_sweep_finish_kernel(const ScatSweepA
   if (i >= a.n_lags * a.k_count) return;
   const long lag = i / a.k_count, kc = i - lag * a.k_count;
   const long y = kc / NC;
-  const int c = (int)(kc - y * NC);
-  const long lb = lag >> 6;
-  const int lane = (int)(lag & 63);
-  const long per_row = a.P * a.lag_blocks;
-  double sum = 0.0;
-  for (long p = 0; p < a.P; ++p) sum += a.part[(size_t)(y * per_row + p * a.lag_blocks + lb) * (NC * 64) + c * 64 + lane];
-  a.sums[lag * a.K + a.k0 + kc] += sum;
+  a.sums[lag * a.K + a.k0 + kc] += lag_sweep_partial_sum<NC>(a, y, lag >> 6, (int)(kc - y * NC), (int)(lag & 63));
 }
 
 }  // namespace rmb

@@ -24,23 +24,9 @@ import sys
 
 import numpy as np
 
-ORIGINS = ("window", "all")
-UPLOAD_BYTES = 64 << 20       # frames go to the device in pieces of at most this many bytes (and at least n_lags frames)
+from ._lagged import ORIGINS, LagAccumulator, counts_per_lag      # ORIGINS and counts_per_lag are this module's names too
+
 TRIU = np.triu_indices(6)
-
-
-def counts_per_lag(n_frames, n_bodies, n_lags, origins="window"):
-  """Number of terms of every lag's sum, int64 (n_lags,): bodies x origins of the convention `origins`."""
-  n_frames, n_bodies, n_lags = int(n_frames), int(n_bodies), int(n_lags)
-  if n_lags < 1:
-    raise ValueError("n_lags must be at least 1, got %r" % (n_lags,))
-  if origins not in ORIGINS:
-    raise ValueError("origins must be one of %s, got %r" % (ORIGINS, origins))
-  if n_frames < 0 or n_bodies < 0:
-    raise ValueError("n_frames and n_bodies must not be negative")
-  if origins == "window":
-    return np.full(n_lags, n_bodies * max(n_frames - n_lags + 1, 0), dtype=np.int64)
-  return n_bodies * np.maximum(n_frames - np.arange(n_lags, dtype=np.int64), 0)
 
 
 def reference_selection(n_steps, dt, end, burn_in=0, trajectory_length=100):
@@ -73,7 +59,7 @@ def _offsets(offsets, n_bodies):
   return np.ascontiguousarray(p.reshape(n_bodies, 3))
 
 
-class MeanSquareDisplacement(object):
+class MeanSquareDisplacement(LagAccumulator):
   """Accumulates the MSD sums of a trajectory of n_bodies rigid bodies over n_lags lags (lag l = l frames = l dt).
   add_frames(frames) takes frames (k, n_bodies, 7) -- rows x y z s p1 p2 p3, numpy or CUDA float64 tensor -- in any
   number of pieces; only the frames of origins whose lags are not complete yet (at most n_lags - 1) stay on the device
@@ -82,95 +68,29 @@ class MeanSquareDisplacement(object):
   (n_lags,), msd() = sums / counts (nan where a lag has no term), times() = dt * lag, write(path).  offsets: body-frame
   tracking offsets, 3 values for all bodies or (n_bodies, 3).  Quaternions are used as they are, never renormalised.  ctx:
   a single-GPU MobilityContext (its resident configuration is left alone); None makes one on `device`, closed by close()."""
+  width, entry = 7, "msd_frames_device"
+  what, row = "the mean-square displacement runs", ("n_bodies", "%d bodies x 7 numbers")
 
   def __init__(self, n_bodies, n_lags, dt=1.0, origins="window", offsets=None, device=0, ctx=None):
-    self.n_bodies, self.n_lags, self.dt = int(n_bodies), int(n_lags), float(dt)
-    if self.n_bodies < 0:
-      raise ValueError("n_bodies must not be negative")
-    counts_per_lag(0, self.n_bodies, self.n_lags, origins)      # refuses what the kernel entry would
-    self.origins = origins
+    LagAccumulator.__init__(self, n_bodies, n_lags, dt, origins)
+    self.n_bodies = self.n
     off = _offsets(offsets, self.n_bodies)
-    self.n_frames = 0
-    self._finished = False
-    self._own_ctx = ctx is None
-    if ctx is None:
-      from .context import MobilityContext
-      ctx = MobilityContext(int(device))
-    if not hasattr(ctx, "msd_frames_device"):
-      if self._own_ctx:
-        ctx.close()
-      raise ValueError("the mean-square displacement runs on a single-GPU MobilityContext, got %r" % (type(ctx).__name__,))
-    self.ctx = ctx
-    import torch
-    self._torch = torch
-    self._dev = torch.device("cuda", ctx.device)
+    self._open(device, ctx)
+    torch = self._torch
     self._sums = torch.zeros((self.n_lags, 6, 6), dtype=torch.float64, device=self._dev)
     self._counts = np.zeros(self.n_lags, dtype=np.int64)
     self._offsets = None if off is None else torch.from_numpy(off).to(self._dev)
-    self._tail = None      # frames of the origins whose lags are not complete yet
 
-  def close(self):
-    if self._own_ctx and self.ctx is not None:
-      self.ctx.close()
-    self.ctx = None
-
-  def _call(self, frames, origins):
+  def _call(self, records, origins):
     with self._torch.cuda.device(self._dev):
-      _, n = self.ctx.msd_frames_device(frames, self.n_lags, offsets=self._offsets, origins=origins, out=self._sums)
+      _, n = self.ctx.msd_frames_device(records[0], self.n_lags, offsets=self._offsets, origins=origins, out=self._sums)
     self._counts += n
-
-  def _add_device(self, piece):
-    """piece: CUDA float64 tensor (k, n_bodies, 7)"""
-    torch = self._torch
-    buf = piece.contiguous() if self._tail is None else torch.cat([self._tail, piece])
-    complete = buf.shape[0] - self.n_lags + 1      # origins of the buffer that have every lag
-    if complete > 0:
-      self._call(buf, "window")
-      buf = buf[complete:].clone()
-    self._tail = buf if buf.shape[0] else None
-    self.n_frames += int(piece.shape[0])
-
-  def add_frames(self, frames):
-    if self._finished:
-      raise ValueError("add_frames() after finish()")
-    torch = self._torch
-    row = 7 * self.n_bodies
-    per = max(self.n_lags, UPLOAD_BYTES // (8 * max(row, 1)))
-    if isinstance(frames, torch.Tensor):
-      if not (frames.is_cuda and frames.dtype == torch.float64):
-        raise ValueError("frames must be a numpy array or a CUDA float64 tensor")
-      if row == 0 or frames.numel() % row:
-        raise ValueError("frames must hold whole frames of %d bodies x 7 numbers, got shape %r" % (self.n_bodies, tuple(frames.shape)))
-      f = frames.reshape(-1, self.n_bodies, 7)
-      for k in range(0, f.shape[0], per):
-        self._add_device(f[k:k + per])
-      return self
-    f = np.ascontiguousarray(frames, dtype=np.float64)
-    if row == 0 or f.size % row:
-      raise ValueError("frames must hold whole frames of %d bodies x 7 numbers, got shape %r" % (self.n_bodies, f.shape))
-    f = f.reshape(-1, self.n_bodies, 7)
-    for k in range(0, f.shape[0], per):
-      piece = f[k:k + per]
-      self._add_device(torch.from_numpy(piece if piece.flags.writeable else piece.copy()).to(self._dev))
-    return self
-
-  def finish(self):
-    """End of the trajectory.  origins="all": the frames still held are origins of the lags that exist for them."""
-    if not self._finished:
-      if self.origins == "all" and self._tail is not None:
-        self._call(self._tail, "all")
-      self._tail = None
-      self._finished = True
-    return self
 
   def sums(self):
     return self._sums.cpu().numpy()
 
   def counts(self):
     return self._counts.copy()
-
-  def times(self):
-    return self.dt * np.arange(self.n_lags)
 
   def msd(self):
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -211,29 +131,12 @@ def reference_msd(locations, orientations, dt, end, burn_in=0, trajectory_length
 
 def load_trajectory(path_or_paths, n_bodies, skip=0):
   """Frames of a `.config` trajectory as (n_frames, n_bodies, 7): one count line, then `x y z s p1 p2 p3` per body, repeated
-  for every saved step; or a list of such files.  The first `skip` frames are left out."""
-  if int(skip) < 0:
-    raise ValueError("skip must not be negative, got %r" % (skip,))
-  paths = [path_or_paths] if isinstance(path_or_paths, (str, bytes)) or hasattr(path_or_paths, "__fspath__") else list(path_or_paths)
-  n_bodies = int(n_bodies)
-  if n_bodies < 1:
+  for every saved step; or a list of such files.  The first `skip` frames are left out.  (correlation.load_trajectory with all
+  seven columns.)"""
+  from .correlation import load_trajectory as load
+  if int(n_bodies) < 1:
     raise ValueError("n_bodies must be at least 1")
-  block = 1 + 7 * n_bodies
-  out = []
-  for path in paths:
-    with open(path) as f:
-      tok = np.array(f.read().split(), dtype=np.float64)
-    if tok.size % block:
-      raise ValueError("%s: %d numbers are not a whole number of frames of %d bodies (1 + 7 * %d numbers each)" % (path, tok.size, n_bodies, n_bodies))
-    tok = tok.reshape(-1, block)
-    if tok.size and np.any(tok[:, 0] != n_bodies):
-      raise ValueError("%s: a frame announces %d bodies, expected %d" % (path, int(tok[tok[:, 0] != n_bodies][0, 0]), n_bodies))
-    out.append(tok[:, 1:].reshape(-1, n_bodies, 7))
-  frames = np.ascontiguousarray(np.concatenate(out)) if out else np.zeros((0, n_bodies, 7))
-  frames = frames[int(skip):]
-  if frames.shape[0] < 1:
-    raise ValueError("no frame left after skipping %d" % int(skip))
-  return frames
+  return load(path_or_paths, n_bodies, skip, columns=7)
 
 
 def main(argv=None, out=None):

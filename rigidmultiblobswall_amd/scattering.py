@@ -27,19 +27,11 @@ import sys
 
 import numpy as np
 
-from .msd import ORIGINS, counts_per_lag
+from ._lagged import ORIGINS, UPLOAD_BYTES, LagAccumulator, lengths as _lengths
 
 PLANES = ("xy", "xyz")
-UPLOAD_BYTES = 64 << 20       # frames go to the device in pieces of at most this many bytes (and at least n_lags frames)
 MAX_WAVEVECTORS = 16384       # per call of the kernel entries
 MAX_INDEX = 32768
-
-
-def _lengths(periodic_length):
-  L = np.asarray(periodic_length, dtype=np.float64).reshape(-1)
-  if L.size != 3:
-    raise ValueError("periodic_length must hold three lengths, got %r" % (periodic_length,))
-  return L.copy()
 
 
 def k_vectors(periodic_length, wavevectors):
@@ -102,7 +94,7 @@ def _check_wavevectors(periodic_length, wv):
   return np.ascontiguousarray(k, dtype=np.int32)
 
 
-class IntermediateScattering(object):
+class IntermediateScattering(LagAccumulator):
   """Accumulates the lag sums of a trajectory of n_points points over n_lags lags (lag l = l frames = l dt) for the
   integer wavevectors `wavevectors` (K, 3) in the box periodic_length.  add_frames(frames) takes frames (k, n_points, 3),
   numpy or CUDA float64 tensor, in any number of pieces; between calls only the density modes of the last n_lags - 1 frames
@@ -111,101 +103,38 @@ class IntermediateScattering(object):
   origins per lag, msd.counts_per_lag for one body; times() = dt * lag; S() (K,), F() and Fs() (n_lags, K), nan where a lag
   has no origin; shells(n_bins) averages over shells of |k|; write(path).  n_lags=1 is the plain structure factor.  ctx: a
   single-GPU MobilityContext (its resident configuration is left alone); None makes one on `device`, closed by close()."""
+  width, entry = 3, "density_modes_frames_device"
+  what, row = "the scattering functions run", ("n_points", "%d points x 3 coordinates")
 
   def __init__(self, n_points, periodic_length, wavevectors, n_lags=1, dt=1.0, origins="window", self_part=False, device=0, ctx=None):
-    self.n_points, self.n_lags, self.dt = int(n_points), int(n_lags), float(dt)
-    if self.n_points < 0:
-      raise ValueError("n_points must not be negative")
-    counts_per_lag(0, 1, self.n_lags, origins)      # refuses what the kernel entries would
-    self.origins, self.self_part = origins, bool(self_part)
+    LagAccumulator.__init__(self, n_points, n_lags, dt, origins)
+    self.n_points, self.self_part = self.n, bool(self_part)
     self.periodic_length = _lengths(periodic_length)
     self.wavevectors = _check_wavevectors(self.periodic_length, wavevectors)
     self.K = int(self.wavevectors.shape[0])
     self.k = k_vectors(self.periodic_length, self.wavevectors)
     self.k_norm = np.sqrt(np.sum(self.k ** 2, axis=1))
-    self.n_frames = 0
-    self._finished = False
-    self._own_ctx = ctx is None
-    if ctx is None:
-      from .context import MobilityContext
-      ctx = MobilityContext(int(device))
-    if not hasattr(ctx, "density_modes_frames_device"):
-      if self._own_ctx:
-        ctx.close()
-      raise ValueError("the scattering functions run on a single-GPU MobilityContext, got %r" % (type(ctx).__name__,))
-    self.ctx = ctx
-    import torch
-    self._torch = torch
-    self._dev = torch.device("cuda", ctx.device)
+    self._open(device, ctx)
+    torch = self._torch
     self._C = torch.zeros((self.n_lags, self.K), dtype=torch.float64, device=self._dev)
     self._Sf = torch.zeros((self.n_lags, self.K), dtype=torch.float64, device=self._dev) if self.self_part else None
     self._counts = np.zeros(self.n_lags, dtype=np.int64)
-    self._tail_modes = None      # modes of the origins whose lags are not complete yet
-    self._tail_frames = None     # their frames (self part only)
 
-  def close(self):
-    if self._own_ctx and self.ctx is not None:
-      self.ctx.close()
-    self.ctx = None
+  def _per(self):
+    return max(self.n_lags, min(UPLOAD_BYTES // (8 * max(3 * self.n_points, 1)), (4 * UPLOAD_BYTES) // (16 * max(self.K, 1))))
 
-  def _call(self, modes, frames, origins):
+  def _records(self, piece):
+    """the modes of every frame, and the frames themselves for the self part"""
     with self._torch.cuda.device(self._dev):
-      _, n = self.ctx.scattering_lags_device(modes, self.n_lags, origins=origins, out=self._C)
-      if self.self_part:
-        self.ctx.self_scattering_frames_device(frames, self.periodic_length, self.wavevectors, self.n_lags, origins=origins, out=self._Sf)
-    self._counts += n
-
-  def _add_device(self, piece):
-    """piece: contiguous CUDA float64 tensor (k, n_points, 3)"""
-    torch = self._torch
-    with torch.cuda.device(self._dev):
       modes = self.ctx.density_modes_frames_device(piece, self.periodic_length, self.wavevectors)
-    if self._tail_modes is not None:
-      modes = torch.cat([self._tail_modes, modes])
-    frames = None
-    if self.self_part:
-      frames = piece if self._tail_frames is None else torch.cat([self._tail_frames, piece])
-    complete = modes.shape[0] - self.n_lags + 1      # origins of the buffer that have every lag
-    if complete > 0:
-      self._call(modes, frames, "window")
-      modes = modes[complete:].clone()
-      frames = frames[complete:].clone() if self.self_part else None
-    self._tail_modes = modes if modes.shape[0] else None
-    self._tail_frames = frames if self.self_part and frames.shape[0] else None
-    self.n_frames += int(piece.shape[0])
+    return (modes, piece) if self.self_part else (modes,)
 
-  def add_frames(self, frames):
-    if self._finished:
-      raise ValueError("add_frames() after finish()")
-    torch = self._torch
-    row = 3 * self.n_points
-    per = max(self.n_lags, min(UPLOAD_BYTES // (8 * max(row, 1)), (4 * UPLOAD_BYTES) // (16 * max(self.K, 1))))
-    if isinstance(frames, torch.Tensor):
-      if not (frames.is_cuda and frames.dtype == torch.float64):
-        raise ValueError("frames must be a numpy array or a CUDA float64 tensor")
-      if row == 0 or frames.numel() % row:
-        raise ValueError("frames must hold whole frames of %d points x 3 coordinates, got shape %r" % (self.n_points, tuple(frames.shape)))
-      f = frames.reshape(-1, self.n_points, 3)
-      for k in range(0, f.shape[0], per):
-        self._add_device(f[k:k + per].contiguous())
-      return self
-    f = np.ascontiguousarray(frames, dtype=np.float64)
-    if row == 0 or f.size % row:
-      raise ValueError("frames must hold whole frames of %d points x 3 coordinates, got shape %r" % (self.n_points, f.shape))
-    f = f.reshape(-1, self.n_points, 3)
-    for k in range(0, f.shape[0], per):
-      piece = f[k:k + per]
-      self._add_device(torch.from_numpy(piece if piece.flags.writeable else piece.copy()).to(self._dev))
-    return self
-
-  def finish(self):
-    """End of the trajectory.  origins="all": the frames still held are origins of the lags that exist for them."""
-    if not self._finished:
-      if self.origins == "all" and self._tail_modes is not None:
-        self._call(self._tail_modes, self._tail_frames, "all")
-      self._tail_modes = self._tail_frames = None
-      self._finished = True
-    return self
+  def _call(self, records, origins):
+    with self._torch.cuda.device(self._dev):
+      _, n = self.ctx.scattering_lags_device(records[0], self.n_lags, origins=origins, out=self._C)
+      if self.self_part:
+        self.ctx.self_scattering_frames_device(records[1], self.periodic_length, self.wavevectors, self.n_lags, origins=origins, out=self._Sf)
+    self._counts += n
 
   def collective_sums(self):
     return self._C.cpu().numpy()
@@ -217,9 +146,6 @@ class IntermediateScattering(object):
 
   def counts(self):
     return self._counts.copy()
-
-  def times(self):
-    return self.dt * np.arange(self.n_lags)
 
   def _normalised(self, sums):
     with np.errstate(divide="ignore", invalid="ignore"):

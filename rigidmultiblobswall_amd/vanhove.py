@@ -32,19 +32,11 @@ import sys
 import numpy as np
 
 from .correlation import normalise
-from .msd import ORIGINS, counts_per_lag
+from ._lagged import ORIGINS, LagAccumulator, counts_per_lag, lengths as _lengths
 
 PLANES = ("xy", "xyz")
 NORMALISATIONS = ("3d", "2d", "pseudo2d")
-UPLOAD_BYTES = 64 << 20       # frames go to the device in pieces of at most this many bytes (and at least n_lags frames)
 MAX_BINS = 8192
-
-
-def _lengths(periodic_length):
-  L = np.asarray(periodic_length, dtype=np.float64).reshape(-1)
-  if L.size != 3:
-    raise ValueError("periodic_length must hold three lengths, got %r" % (periodic_length,))
-  return L.copy()
 
 
 def shell_volumes(r_max, n_bins, plane):
@@ -86,7 +78,7 @@ def alpha2_from_moments(moments, counts, plane):
   return r2, np.where(r2 > 0, a2, np.nan)
 
 
-class VanHove(object):
+class VanHove(LagAccumulator):
   """Accumulates the van Hove counts of a trajectory of n_points points over n_lags lags (lag l = l frames = l dt) in the box
   periodic_length (<= 0: open direction).  Distinct part: n_bins bins up to r_max (None: half the smallest positive period of
   the plane); self part: self_n_bins bins up to self_r_max (None: the distinct values).  add_frames(frames) takes frames
@@ -96,16 +88,16 @@ class VanHove(object):
   lag; counts(): terms per lag (msd.counts_per_lag); times(), r(), r_self(); self_counts(), distinct_counts(); Gs(), Gd(),
   msd(), alpha2(); write(path).  distinct=False leaves the O(N^2) part out.  ctx: a single-GPU MobilityContext (its
   resident configuration is left alone); None makes one on `device`, closed by close()."""
+  width, entry = 3, "van_hove_self_frames_device"
+  what, row = "the van Hove functions run", ("n_points", "%d points x 3 coordinates")
 
   def __init__(self, n_points, periodic_length, n_lags, dt=1.0, r_max=None, n_bins=1000, self_r_max=None, self_n_bins=None,
                origins="window", plane="xyz", distinct=True, device=0, ctx=None):
-    self.n_points, self.n_lags, self.dt = int(n_points), int(n_lags), float(dt)
-    if self.n_points < 0:
-      raise ValueError("n_points must not be negative")
-    counts_per_lag(0, 1, self.n_lags, origins)      # refuses what the kernel entries would
+    LagAccumulator.__init__(self, n_points, n_lags, dt, origins)
+    self.n_points = self.n
     if plane not in PLANES:
       raise ValueError("plane must be one of %s, got %r" % (PLANES, plane))
-    self.origins, self.plane, self.distinct = origins, plane, bool(distinct)
+    self.plane, self.distinct = plane, bool(distinct)
     self.periodic_length = _lengths(periodic_length)
     if r_max is None:
       periods = self.periodic_length[:2 if plane == "xy" else 3]
@@ -120,32 +112,15 @@ class VanHove(object):
         raise ValueError("%s must be positive and finite, got %r" % (name, r))
       if not 1 <= b <= MAX_BINS:
         raise ValueError("the number of bins must be 1 ... %d, got %r" % (MAX_BINS, b))
-    self.n_frames = 0
-    self._finished = False
-    self._own_ctx = ctx is None
-    if ctx is None:
-      from .context import MobilityContext
-      ctx = MobilityContext(int(device))
-    if not hasattr(ctx, "van_hove_self_frames_device"):
-      if self._own_ctx:
-        ctx.close()
-      raise ValueError("the van Hove functions run on a single-GPU MobilityContext, got %r" % (type(ctx).__name__,))
-    self.ctx = ctx
-    import torch
-    self._torch = torch
-    self._dev = torch.device("cuda", ctx.device)
+    self._open(device, ctx)
+    torch = self._torch
     self._Hs = torch.zeros((self.n_lags, self.self_n_bins), dtype=torch.int64, device=self._dev)
     self._M = torch.zeros((self.n_lags, 2), dtype=torch.float64, device=self._dev)
     self._Hd = torch.zeros((self.n_lags, self.n_bins), dtype=torch.int64, device=self._dev) if self.distinct else None
     self._origins = np.zeros(self.n_lags, dtype=np.int64)
-    self._tail = None      # the frames whose lags are not complete yet
 
-  def close(self):
-    if self._own_ctx and self.ctx is not None:
-      self.ctx.close()
-    self.ctx = None
-
-  def _call(self, frames, origins):
+  def _call(self, records, origins):
+    frames, = records
     with self._torch.cuda.device(self._dev):
       self.ctx.van_hove_self_frames_device(frames, self.n_lags, self.self_r_max, self.self_n_bins, origins=origins, plane=self.plane,
                                            out=self._Hs, moments=self._M)
@@ -154,57 +129,11 @@ class VanHove(object):
                                                  plane=self.plane, out=self._Hd)
     self._origins += counts_per_lag(int(frames.shape[0]), 1, self.n_lags, origins)
 
-  def _add_device(self, piece):
-    """piece: contiguous CUDA float64 tensor (k, n_points, 3)"""
-    frames = piece if self._tail is None else self._torch.cat([self._tail, piece])
-    complete = frames.shape[0] - self.n_lags + 1      # origins of the buffer that have every lag
-    if complete > 0:
-      self._call(frames, "window")
-      frames = frames[complete:].clone()
-    self._tail = frames if frames.shape[0] else None
-    self.n_frames += int(piece.shape[0])
-
-  def add_frames(self, frames):
-    if self._finished:
-      raise ValueError("add_frames() after finish()")
-    torch = self._torch
-    row = 3 * self.n_points
-    per = max(self.n_lags, UPLOAD_BYTES // (8 * max(row, 1)))
-    if isinstance(frames, torch.Tensor):
-      if not (frames.is_cuda and frames.dtype == torch.float64):
-        raise ValueError("frames must be a numpy array or a CUDA float64 tensor")
-      if row == 0 or frames.numel() % row:
-        raise ValueError("frames must hold whole frames of %d points x 3 coordinates, got shape %r" % (self.n_points, tuple(frames.shape)))
-      f = frames.reshape(-1, self.n_points, 3)
-      for k in range(0, f.shape[0], per):
-        self._add_device(f[k:k + per].contiguous())
-      return self
-    f = np.ascontiguousarray(frames, dtype=np.float64)
-    if row == 0 or f.size % row:
-      raise ValueError("frames must hold whole frames of %d points x 3 coordinates, got shape %r" % (self.n_points, f.shape))
-    f = f.reshape(-1, self.n_points, 3)
-    for k in range(0, f.shape[0], per):
-      piece = f[k:k + per]
-      self._add_device(torch.from_numpy(piece if piece.flags.writeable else piece.copy()).to(self._dev))
-    return self
-
-  def finish(self):
-    """End of the trajectory.  origins="all": the frames still held are origins of the lags that exist for them."""
-    if not self._finished:
-      if self.origins == "all" and self._tail is not None:
-        self._call(self._tail, "all")
-      self._tail = None
-      self._finished = True
-    return self
-
   def n_origins(self):
     return self._origins.copy()
 
   def counts(self):
     return self._origins * self.n_points
-
-  def times(self):
-    return self.dt * np.arange(self.n_lags)
 
   def r(self):
     return (np.arange(self.n_bins) + 0.5) * (self.r_max / self.n_bins)

@@ -175,7 +175,7 @@ def test_streamed_in_uneven_chunks(ctx, origins):
   one_shot, counts = ctx.msd_frames_device(_dev(frames), L, offsets=offsets, origins=origins)
   acc = msd.MeanSquareDisplacement(N, L, dt=0.25, origins=origins, offsets=offsets, ctx=ctx)
   acc.add_frames(frames[:1]).add_frames(torch.from_numpy(frames[1:6]).cuda()).add_frames(frames[6:])
-  assert acc._tail is not None and acc._tail.shape[0] == L - 1      # only the origins whose lags are not complete are kept
+  assert acc._tail is not None and [t.shape[0] for t in acc._tail] == [L - 1]      # only the origins whose lags are not complete are kept
   acc.finish()
   assert np.array_equal(acc.counts(), n) and np.array_equal(acc.counts(), counts) and acc.n_frames == F
   _within(acc.sums(), S_ld, tol, "streamed")

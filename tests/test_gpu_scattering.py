@@ -323,7 +323,7 @@ def test_streamed_in_pieces(ctx, origins):
       piece = frames[start:start + size]
       acc.add_frames(torch.from_numpy(piece.copy()).cuda() if i % 2 else piece)
       start += size
-    assert start == F and acc._tail_modes.shape[0] == L - 1 and acc._tail_frames.shape[0] == L - 1      # only the incomplete origins are kept
+    assert start == F and [t.shape[0] for t in acc._tail] == [L - 1, L - 1]      # modes and frames: only the incomplete origins are kept
     acc.finish()
     assert np.array_equal(acc.counts(), n_o) and np.array_equal(acc.counts(), msd.counts_per_lag(F, 1, L, origins)) and acc.n_frames == F
     _sums_within("collective", acc.collective_sums(), C_ld, snp.collective_bound(n_o, A), "streamed %s %s" % (origins, pieces))
