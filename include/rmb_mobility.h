@@ -423,6 +423,37 @@ int rmb_body_body_force_device(rmb_ctx* ctx, double repulsion_strength, double d
  * The *_device variant writes the one double to device memory, asynchronously on the context's stream. */
 int rmb_body_body_potential(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_host);
 int rmb_body_body_potential_device(rmb_ctx* ctx, double repulsion_strength, double debye_length, double* out_dev);
+/* A blob-blob pair law given as a table: a radial law U(r) of K uniform intervals of width h from r0, one cubic per
+ * interval, coeff_host[K][4] = (c0, c1, c2, c3) in fp64; r_cut = r0 + K h.
+ *   r0 <= r < r_cut:  x = (r - r0)/h, k = min(floor(x), K - 1), t = x - k,
+ *                     U = c0 + t (c1 + t (c2 + t c3)),  U' = (c1 + t (2 c2 + 3 t c3)) / h
+ *   r < r0:           U = c[0][0] + (c[0][1]/h)(r - r0),  U' = c[0][1]/h      (a linear core, constant force magnitude)
+ *   r >= r_cut:       U = U' = +0.0 exactly
+ * The force on blob i is (U'(r)/r)(r_j - r_i), evaluated as U'(r) min(1/r, 1e25) (r_j - r_i): coincident blobs get a zero
+ * force and the energy c[0][0] - c[0][1] r0 / h.  Force and energy are consistent by construction: the force is the exact
+ * derivative of the interpolant whose value is the energy.  rmb_ctx_set_pair_table copies the table into the context
+ * (synchronous; coeff_host is the caller's again on return) and replaces the one that was there; n_intervals = 0 clears it.
+ * Refused with RMB_ERR_ARG before anything touches a device: n_intervals < 0 or > 1024, h not finite or <= 0, r0 negative
+ * or not finite, a coefficient that is not finite, a null coeff_host with n_intervals > 0.  Uniform radius-free law, fp64
+ * only; per-blob radii, "precision" = 32, pair shards and the multi-device engine do not serve it.
+ *
+ * rmb_pair_table_force: out (n,3), the forces of that law on the resident points (rmb_set_positions with wall = 0; wall = 1
+ * or a target sub-range: RMB_ERR_STATE, as is a context without a table), minimal image in every direction with a positive
+ * period.  Each unordered pair once on the symmetric force sweep whatever n, "symmetric", "deterministic" and "precision"
+ * say (atomic flushes; last_path = 1); the K records are staged in K * 32 bytes of LDS per workgroup.  "force_cull" (tile
+ * pairs beyond r_cut: exact zeros) and "force_sort" apply.
+ *
+ * rmb_blob_potential_table: rmb_blob_potential with the pair term taken from the table -- out = {U_one_blob, U_pair}; the
+ * one-blob arguments, `form` (which now chooses the one-blob expression only), the wall gate (a blob with z <= 0 contributes
+ * 1e5 (1 - z) and no pair term as the lower of the caller's two indices) and the minimal image in x and y only are
+ * rmb_blob_potential's.  No atomics; tile culling by r_cut. */
+int rmb_ctx_set_pair_table(rmb_ctx* ctx, double r0, double h, long n_intervals, const double* coeff_host);
+int rmb_pair_table_force(rmb_ctx* ctx, double* out_host);
+int rmb_pair_table_force_device(rmb_ctx* ctx, double* out_dev);
+int rmb_blob_potential_table(rmb_ctx* ctx, double repulsion_strength_wall, double debye_length_wall, double weight,
+                             double blob_radius, int form, double* out_host);
+int rmb_blob_potential_table_device(rmb_ctx* ctx, double repulsion_strength_wall, double debye_length_wall, double weight,
+                                    double blob_radius, int form, double* out_dev);
 /* Histogram of the pair distances of the resident points: the counts behind the radial distribution function g(r)
  * (multi_bodies/examples/Radial_Dist_Test/gr_pseudo2D_single_blob.cpp).  Uses the raw positions as rmb_blob_potential
  * (rmb_set_positions with wall = 0; wall = 1 or a target sub-range: RMB_ERR_STATE).  For every unordered pair i < j:

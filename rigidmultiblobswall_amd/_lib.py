@@ -76,6 +76,11 @@ SYMBOLS = {
     "rmb_body_body_force_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_body_body_potential": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     "rmb_body_body_potential_device": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "rmb_ctx_set_pair_table": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_long, _vp]),
+    "rmb_pair_table_force": (ctypes.c_int, [_vp, _vp]),
+    "rmb_pair_table_force_device": (ctypes.c_int, [_vp, _vp]),
+    "rmb_blob_potential_table": (ctypes.c_int, [_vp] + [ctypes.c_double] * 4 + [ctypes.c_int, _vp]),
+    "rmb_blob_potential_table_device": (ctypes.c_int, [_vp] + [ctypes.c_double] * 4 + [ctypes.c_int, _vp]),
     "rmb_blob_potential": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_blob_potential_device": (ctypes.c_int, [_vp] + [ctypes.c_double] * 6 + [ctypes.c_int, _vp]),
     "rmb_pair_histogram": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_long, _vp]),

@@ -560,6 +560,44 @@ class MobilityContext(object):
                                                         ctypes.c_void_p(out.data_ptr())))
     return out
 
+  def set_pair_table(self, table):
+    """Copies a PairTable (pair_table.py: a radial pair law as K cubics) into the context, replacing the one that was
+    there; None clears it (rmb_ctx_set_pair_table).  pair_table_force and blob_potential(..., pair_table=...) run on it."""
+    from .pair_table import PairTable
+    if table is None:
+      _lib.check(self._lib.rmb_ctx_set_pair_table(self._h, 0.0, 1.0, 0, None))
+    else:
+      if not isinstance(table, PairTable):
+        raise ValueError("set_pair_table takes a PairTable or None, got %r" % (type(table).__name__,))
+      c = np.ascontiguousarray(table.coeff, dtype=np.float64)
+      _lib.check(self._lib.rmb_ctx_set_pair_table(self._h, table.r0, table.h, table.K, _ptr(c)))
+    self._pair_table = table
+
+  def _use_pair_table(self, table):
+    """pair_table= of a call: make `table` the context's (a copy only when it is not already)."""
+    if table is not getattr(self, "_pair_table", None):
+      self.set_pair_table(table)
+
+  def pair_table_force(self):
+    """(n, 3) blob-blob forces of the context's pair table on the resident raw positions (set_positions(..., wall=False)):
+    F_i = sum_j (U'(r)/r) (x_j - x_i), minimal image in every periodic direction; always the symmetric fp64 sweep
+    (rmb_pair_table_force)."""
+    out = np.empty(3 * self.n)
+    _lib.check(self._lib.rmb_pair_table_force(self._h, _ptr(out)))
+    return out.reshape(self.n, 3)
+
+  def pair_table_force_device(self, out=None, device=None):
+    """The same as a CUDA float64 tensor of 3 n entries, asynchronous on the context's stream
+    (rmb_pair_table_force_device); a caller's out= goes straight to the kernel."""
+    import torch
+    if out is None:
+      out = torch.empty(3 * self.n, dtype=torch.float64, device=device or ("cuda:%d" % self.device))
+    elif not _is_torch_cuda(out) or out.dtype != torch.float64 or out.numel() != 3 * self.n or not out.is_contiguous():
+      raise ValueError("out must be a contiguous CUDA float64 tensor with 3*n entries")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_pair_table_force_device(self._h, ctypes.c_void_p(out.data_ptr())))
+    return out
+
   def pair_histogram(self, r_max, n_bins):
     """Counts of the unordered pairs i < j of the resident points (set_positions(..., wall=False)) per distance bin:
     r < r_max lands in bin int(r / (r_max / n_bins)), r in the minimal image of every periodic direction (z included), fp64
@@ -756,25 +794,38 @@ class MobilityContext(object):
             float(blob_radius), POTENTIAL_FORMS[potential])
 
   def blob_potential(self, repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0, weight=0.0,
-                     potential="soft"):
+                     potential="soft", pair_table=None):
     """(U_one_blob, U_pair) of the resident raw positions (set_positions(..., wall=False)): the equilibrium sampler's energy,
-    many_body_potential_pycuda.py:15-119 ("soft") or the boomerang example's Yukawa form ("yukawa"); rmb_blob_potential."""
+    many_body_potential_pycuda.py:15-119 ("soft") or the boomerang example's Yukawa form ("yukawa"); rmb_blob_potential.
+    pair_table=T (a PairTable): the pair term is T's (repulsion_strength and debye_length are not read), `potential`
+    still chooses the one-blob form; T becomes the context's table (rmb_blob_potential_table)."""
     out = np.empty(2)
+    if pair_table is not None:
+      self._use_pair_table(pair_table)
+      args = self._potential_args(0.0, 1.0, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
+      _lib.check(self._lib.rmb_blob_potential_table(self._h, *args[2:], _ptr(out)))
+      return float(out[0]), float(out[1])
     _lib.check(self._lib.rmb_blob_potential(self._h, *self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall,
                                                                           debye_length_wall, weight, blob_radius, potential), _ptr(out)))
     return float(out[0]), float(out[1])
 
   def blob_potential_device(self, repulsion_strength, debye_length, blob_radius, repulsion_strength_wall=0.0, debye_length_wall=1.0,
-                            weight=0.0, potential="soft", out=None, device=None):
+                            weight=0.0, potential="soft", out=None, device=None, pair_table=None):
     """The same two sums as a CUDA float64 tensor of two entries, asynchronous on the context's stream
-    (rmb_blob_potential_device).  A caller's out= goes straight to the kernel."""
+    (rmb_blob_potential_device; pair_table=T: rmb_blob_potential_table_device).  A caller's out= goes straight to the kernel."""
     import torch
+    if pair_table is not None:
+      repulsion_strength, debye_length = 0.0, 1.0
     args = self._potential_args(repulsion_strength, debye_length, repulsion_strength_wall, debye_length_wall, weight, blob_radius, potential)
     if out is None:
       out = torch.empty(2, dtype=torch.float64, device=device or ("cuda:%d" % self.device))
     elif not _is_torch_cuda(out) or not out.is_contiguous() or out.numel() != 2:
       raise ValueError("out must be a contiguous CUDA float64 tensor with 2 entries")
     self._follow_torch_stream()
+    if pair_table is not None:
+      self._use_pair_table(pair_table)
+      _lib.check(self._lib.rmb_blob_potential_table_device(self._h, *args[2:], ctypes.c_void_p(out.data_ptr())))
+      return out
     _lib.check(self._lib.rmb_blob_potential_device(self._h, *args, ctypes.c_void_p(out.data_ptr())))
     return out
 

@@ -20,8 +20,13 @@
 // BodyYukawaLaw (sym_force_kernels.h).  The yukawa pair expression with three differences: the minimal image in every direction
 // with a positive period, z included (the image rule of the force law); no wall gate and no one-blob term (a centre with
 // z <= 0 counts in full); one result.  Tile culling by 750 b with the z period in the tile gap.
+//
+// TABLE: the pair term is the context's tabulated radial law (pair_table_kernels.h) instead of the FORM's; the one-blob term,
+// the wall gate and the x-y minimal image are the blob forms' own, FORM still chooses the one-blob expression.  Distinct
+// blobs at r = 0 give the core's finite value c[0][0] - c[0][1] r0 / h.  Tile culling by r_cut.
 #pragma once
 #include "pair_once_kernels.h"
+#include "pair_table_kernels.h"
 
 namespace rmb {
 
@@ -37,6 +42,7 @@ struct PotentialArgs : PairOnceArgs {
   long n_partial;       // n_waves
   double* out;          // {U_one_blob, U_pair}; BODY: {U_body}
   int n_out;            // 2, BODY: 1
+  PairTableRef tab;     // TABLE: the context's pair table; cull2 is its r_cut^2
 };
 
 // exp of any argument from exp_nonpositive: 1 / exp(-x) for x > 0 (one more rounding; inf where exp overflows).  The
@@ -81,6 +87,13 @@ __device__ __forceinline__ double pair_potential(const PotentialArgs& a, double 
   }
 }
 
+// u2 of one pair from the table (separation already the minimal image); r as the soft form takes it: finite at r2 = 0
+__device__ __forceinline__ double table_potential(const PotentialArgs& a, double dx, double dy, double dz) {
+  const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
+  const double r = r2 * rsqrt_f64(fmax(r2, 1e-300));
+  return pair_table_u(a.tab, r2, r);
+}
+
 // separation in z: the blob forms take it as it is, the body centres take its minimal image
 template <bool PERIODIC, bool BODY>
 __device__ __forceinline__ double image_z(const PotentialArgs& a, double d) {
@@ -89,9 +102,10 @@ __device__ __forceinline__ double image_z(const PotentialArgs& a, double d) {
 }
 
 // The energy as a policy of the pair-once frame (pair_once_kernels.h)
-template <int FORM, bool PERIODIC, bool BODY>
+template <int FORM, bool PERIODIC, bool BODY, bool TABLE = false>
 struct PotentialOp {
   static_assert(!BODY || FORM == POT_YUKAWA, "the body-body law is the yukawa pair expression");
+  static_assert(!BODY || !TABLE, "the tabulated law is a blob-blob law");
   typedef PotentialArgs Args;
   struct Lane { double u_one, u_pair; };
   static constexpr bool FRAMES = false;
@@ -118,8 +132,11 @@ struct PotentialOp {
   }
   template <bool GUARDED>
   static __device__ __forceinline__ void pair(const Args& a, Lane& st, const double4& self, const double4& q, bool take) {
-    const double u = pair_potential<FORM>(a, image<PERIODIC>(a.Lx, a.iLx, self.x - q.x), image<PERIODIC>(a.Ly, a.iLy, self.y - q.y),
-                                          image_z<PERIODIC, BODY>(a, self.z - q.z));
+    const double dx = image<PERIODIC>(a.Lx, a.iLx, self.x - q.x), dy = image<PERIODIC>(a.Ly, a.iLy, self.y - q.y);
+    const double dz = image_z<PERIODIC, BODY>(a, self.z - q.z);
+    double u;
+    if constexpr (TABLE) u = table_potential(a, dx, dy, dz);
+    else                 u = pair_potential<FORM>(a, dx, dy, dz);
     if constexpr (GUARDED) {
       const double z_low = self.w < q.w ? self.z : q.z;      // the blob with the lower caller's index decides
       const bool real = self.w < 1e17 && q.w < 1e17;         // padding carries index PAD_W
@@ -130,10 +147,11 @@ struct PotentialOp {
   }
 };
 
-template <int FORM, bool PERIODIC, bool BODY = false>
+template <int FORM, bool PERIODIC, bool BODY = false, bool TABLE = false>
 __global__ __launch_bounds__(64 * kSymWaves) void potential_kernel(const PotentialArgs a) {
-  typedef PotentialOp<FORM, PERIODIC, BODY> OP;
+  typedef PotentialOp<FORM, PERIODIC, BODY, TABLE> OP;
   __shared__ double4 rec_all[kSymWaves][64];
+  if constexpr (TABLE) stage_pair_table(a.tab);      // once per workgroup, before any wave starts its walk
   typename OP::Lane st{0.0, 0.0};
   pair_once_sweep<OP>(a, st, rec_all[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
   // fixed butterfly over the lanes, one pair of partials per wave

@@ -131,6 +131,19 @@ int body_force_device_impl(rmb_ctx* c, double eps, double b, double* out) {
   return sym_force_device(c, eps, b, 0.0, out, nullptr, 0, 1, FORCE_LAW_BODY);
 }
 
+// Blob-blob forces of the context's tabulated law: the body-body rule -- always the symmetric fp64 sweep, raw positions, all
+// resident points.
+int table_force_device_impl(rmb_ctx* c, double* out) {
+  if (int rc = check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  if (c->tab_k == 0) return fail(RMB_ERR_STATE, "no pair table is set: call rmb_ctx_set_pair_table");
+  if (c->wall) return fail(RMB_ERR_STATE, "the tabulated pair force uses raw positions: call rmb_set_positions with wall = 0");
+  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "the tabulated pair force acts on all resident points: reset the target range");
+  if (c->n == 0) return 0;
+  RMB_HIP(hipSetDevice(c->device));
+  return sym_force_device(c, 0.0, 1.0, 0.0, out, nullptr, 0, 1, FORCE_LAW_TABLE);
+}
+
 // Multi-block operations (include/rmb_mobility.h, enum rmb_op).  One symmetric pass when that path applies (or for a
 // pair shard); otherwise composed from the one-sided sweeps (target sub-ranges, "deterministic", n < 128).
 // One pair shard of a single-vector product.  `in_plane` (the reference's in_plane_* wrappers: z row / column masked) is
@@ -507,6 +520,45 @@ int rmb_body_body_force(rmb_ctx* c, double eps, double b, double* out) {
   const size_t ob = (size_t)3 * c->n * sizeof(double);
   if (int rc = c->out.reserve(ob)) return rc;
   if (int rc = body_force_device_impl(c, eps, b, (double*)c->out.p)) return rc;
+  return download(c, out, c->out.p, ob);
+}
+
+int rmb_ctx_set_pair_table(rmb_ctx* c, double r0, double h, long n_intervals, const double* coeff_host) {
+  // the arguments first: none of these checks needs a device (or a context)
+  if (n_intervals < 0 || n_intervals > rmb::kPairTableMax) return fail(RMB_ERR_ARG, "pair table: n_intervals must be 0 (clear) or 1..1024");
+  if (n_intervals > 0) {
+    if (!std::isfinite(h) || !(h > 0.0)) return fail(RMB_ERR_ARG, "pair table: the interval width h must be finite and positive");
+    if (!std::isfinite(r0) || r0 < 0.0) return fail(RMB_ERR_ARG, "pair table: r0 must be finite and not negative");
+    if (!coeff_host) return fail(RMB_ERR_ARG, "pair table: null coefficient pointer");
+    for (long i = 0; i < 4 * n_intervals; ++i)
+      if (!std::isfinite(coeff_host[i])) return fail(RMB_ERR_ARG, "pair table: coefficient " + std::to_string(i) + " is not finite");
+    if (!std::isfinite(r0 + (double)n_intervals * h) || !std::isfinite(1.0 / h)) return fail(RMB_ERR_ARG, "pair table: r_cut = r0 + K h or 1/h overflows");
+  }
+  if (!c) return fail(RMB_ERR_ARG, "null context");
+  if (n_intervals == 0) { c->tab_k = 0; return 0; }
+  RMB_HIP(hipSetDevice(c->device));
+  const size_t bytes = (size_t)n_intervals * 4 * sizeof(double);
+  // a sweep queued on the stream may still read the old records
+  RMB_HIP(hipStreamSynchronize(c->stream));
+  c->tab_k = 0;
+  if (int rc = c->pair_table.reserve(bytes)) return rc;
+  RMB_HIP(hipMemcpyAsync(c->pair_table.p, coeff_host, bytes, hipMemcpyHostToDevice, c->stream));
+  RMB_HIP(hipStreamSynchronize(c->stream));      // coeff_host is the caller's again
+  c->tab_k = n_intervals; c->tab_r0 = r0; c->tab_h = h;
+  return 0;
+}
+
+int rmb_pair_table_force_device(rmb_ctx* c, double* out) { return table_force_device_impl(c, out); }
+
+int rmb_pair_table_force(rmb_ctx* c, double* out) {
+  if (int rc = check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  if (c->tab_k == 0) return fail(RMB_ERR_STATE, "no pair table is set: call rmb_ctx_set_pair_table");
+  if (c->n == 0) return 0;
+  RMB_HIP(hipSetDevice(c->device));
+  const size_t ob = (size_t)3 * c->n * sizeof(double);
+  if (int rc = c->out.reserve(ob)) return rc;
+  if (int rc = table_force_device_impl(c, (double*)c->out.p)) return rc;
   return download(c, out, c->out.p, ob);
 }
 

@@ -36,6 +36,9 @@
 //   rmb_van_hove.hip  lag histograms behind the van Hove functions G_s(r, t), G_d(r, t) of caller-owned frames
 //                    (van_hove_kernels.h): self sweep (a lane owns a point; counts and the moments sum r^2, sum r^4, finishing
 //                    launch) and distinct sweep over ordered pairs (a workgroup owns a lag; the rotation of the pair-once frame)
+//   pair_table_kernels.h (a header) the tabulated radial pair law: what TableLaw of the force sweep (rmb_sym.hip) and the TABLE
+//                    instances of the energy sweep (rmb_potential.hip) share -- LDS staging, interval lookup, the two cubics;
+//                    rmb_ctx_set_pair_table and the force entry points are in rmb_entry.hip
 //   lag_sweep_host.h (a header, included by the three units above) the checks of a batch of frames and of a lag / origin
 //                    range, pad256, and the one launch plan of the lag sweeps (plan_lag_sweep)
 #pragma once
@@ -50,6 +53,7 @@
 #include <vector>
 
 #include "pair_ops.h"
+#include "pair_table_kernels.h"
 
 namespace rmbi {
 
@@ -100,6 +104,7 @@ struct CtxBuffers {
   DevBuf msd_ws;           // mean-square displacement (rmb_msd.hip): body-major records + per-workgroup partial sums
   DevBuf scat_ws;          // scattering (rmb_scattering.hip): n / L of the wavevectors, series-major records, partial sums
   DevBuf vh_ws;            // van Hove self sweep (rmb_van_hove.hip): per-workgroup partial moments
+  DevBuf pair_table;       // records (c0, c1, c2, c3) of the tabulated pair law (rmb_ctx_set_pair_table)
   DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
   DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
   DevBuf krylov;   // partial sums of rmb_krylov_orthogonalize_device
@@ -109,7 +114,7 @@ struct CtxBuffers {
 using CB = CtxBuffers;
 constexpr DevBuf CB::* kCtxBufs[] = {&CB::pos, &CB::r_stage, &CB::vec, &CB::vec2, &CB::out, &CB::partial, &CB::tmp3n, &CB::tile_bounds,
                                      &CB::fpos, &CB::fperm, &CB::fsort_keys, &CB::fsort_vals, &CB::fsort_tmp, &CB::fsort_box,
-                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::vh_ws, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
+                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::vh_ws, &CB::pair_table, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
 static_assert(sizeof(CtxBuffers) == (sizeof(kCtxBufs) / sizeof(kCtxBufs[0]) + 8) * sizeof(DevBuf),
               "a DevBuf of CtxBuffers is missing from kCtxBufs (or st[] changed its length)");
 template <class Bufs, class F>      // Bufs: CtxBuffers or const CtxBuffers (an rmb_ctx converts)
@@ -142,6 +147,9 @@ struct rmb_ctx : rmbi::CtxBuffers {
   long fperm_n = -1;             // number of blobs fperm is a permutation of (force_sort_positions), -1 = none
   // (potential energy: the Morton permutation is kept and rebuilt every opt_potential_resort-th evaluation -- a Metropolis proposal moves a blob by a tenth of its radius)
   long pot_sort_age = -1;        // evaluations since the permutation was built, -1 = build it now
+  // tabulated pair law (rmb_ctx_set_pair_table): K intervals of width h from r0, records in `pair_table`; K = 0: none
+  long tab_k = 0;
+  double tab_r0 = 0.0, tab_h = 0.0;
   long wave_clock_n = 0;
   long symbuf_zeroed_for = -1;
   void* gmres_ws = nullptr;   // workspace of the native Krylov loops (rmb_gmres.hip), freed by gmres_release
@@ -427,7 +435,10 @@ int symx_device(rmb_ctx* c, int op, const double* const* in, double* const* out,
 int tt_raw_sums_device(rmb_ctx* c, const double* v, double eta, double* out);
 int symx_det_device(rmb_ctx* c, int op, const double* const* in, double* const* out, double eta, int in_plane,
                     long shard = 0, long nshards = 1);
-enum ForceLaw { FORCE_LAW_BLOB = 0, FORCE_LAW_BODY = 1 };   // the pair law of sym_force_kernel (sym_force_kernels.h)
+enum ForceLaw { FORCE_LAW_BLOB = 0, FORCE_LAW_BODY = 1, FORCE_LAW_TABLE = 2 };   // the pair law of sym_force_kernel (sym_force_kernels.h)
+// the context's pair table as the kernels take it (tab_k > 0), and its reach
+rmb::PairTableRef pair_table_ref(const rmb_ctx* c);
+inline double pair_table_rcut(const rmb_ctx* c) { return c->tab_r0 + (double)c->tab_k * c->tab_h; }
 int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, double* out, const double* radii, long shard,
                      long nshards, ForceLaw law = FORCE_LAW_BLOB);
 

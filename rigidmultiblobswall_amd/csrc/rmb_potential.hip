@@ -14,11 +14,15 @@ namespace {
 // `body`: the resident points are body locations and the energy is the body-body Yukawa law's (the BODY instance of
 // potential_kernels.h): the yukawa pair expression without contact distance, wall gate and one-blob term, imaged in all three
 // directions; ONE sum in out_dev[0].
+// `table`: the pair term is the context's tabulated law (the TABLE instances): eps and b are not read, the reach is r_cut,
+// the records are staged in tab_k * 32 bytes of dynamic LDS; the one-blob term and the wall gate are `form`'s as ever.
 int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, double b_wall, double weight, double blob_radius, int form,
-                          double* out_dev, bool body = false) {
+                          double* out_dev, bool body = false, bool table = false) {
   if (int rc = check_ready(c)) return rc;
   if (!out_dev) return fail(RMB_ERR_ARG, "null output pointer");
   if (form != rmb::POT_SOFT && form != rmb::POT_YUKAWA) return fail(RMB_ERR_ARG, "potential form must be 0 (soft) or 1 (yukawa)");
+  if (table && c->tab_k == 0) return fail(RMB_ERR_STATE, "no pair table is set: call rmb_ctx_set_pair_table");
+  if (table) { eps = 0.0; b = 1.0; }
   if (!(b > 0.0)) return fail(RMB_ERR_ARG, "debye_length must be positive");
   if (eps_wall != 0.0 && !(b_wall > 0.0)) return fail(RMB_ERR_ARG, "debye_length_wall must be positive when repulsion_strength_wall is not zero");
   typedef rmb::PotentialArgs A;
@@ -38,22 +42,29 @@ int potential_device_impl(rmb_ctx* c, double eps, double b, double eps_wall, dou
   a.eps_wall = eps_wall; a.inv_b_wall = eps_wall != 0.0 ? 1.0 / b_wall : 0.0; a.a = blob_radius; a.weight = weight;
   a.ec = exp_consts();
   const double reach = form == rmb::POT_SOFT ? 2.0 * blob_radius + 750.0 * b : 750.0 * b;
-  a.cull2 = c->opt_force_cull ? reach * reach : std::numeric_limits<double>::infinity();
+  a.tab = table ? pair_table_ref(c) : rmb::PairTableRef{};
+  a.cull2 = !c->opt_force_cull ? std::numeric_limits<double>::infinity() : table ? a.tab.rcut2 : reach * reach;
+  const size_t dyn_lds = table ? (size_t)c->tab_k * sizeof(double4) : 0;
 
-  const SymKernel k = body ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true, true>>(0)
+  const SymKernel k = table ? (form == rmb::POT_SOFT
+                                   ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, true, false, true>>(0)
+                                               : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, false, false, true>>(0))
+                                   : (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true, false, true>>(0)
+                                               : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false, false, true>>(0)))
+                      : body ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true, true>>(0)
                                        : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false, true>>(0))
                       : form == rmb::POT_SOFT
                           ? (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, true>>(0) : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_SOFT, false>>(0))
                           : (periodic ? sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, true>>(0)
                                       : sym_kernel_of<A, rmb::potential_kernel<rmb::POT_YUKAWA, false>>(0));
   long blocks;
-  plan_cull_sweep(c, k, a.step_end, &blocks, &a.chunk_steps);
+  plan_cull_sweep(c, k, a.step_end, &blocks, &a.chunk_steps, 0, dyn_lds);
   const long waves = blocks * rmb::kSymWaves;
   if (int rc = c->pot_ws.reserve((size_t)(2 * waves + 2) * sizeof(double))) return rc;
   a.partial = (double*)c->pot_ws.p;
   a.n_partial = waves;
   a.out = out_dev;
-  return sym_launch(c, k, 1, blocks, 0, a, rmb::PairConsts{}, rmb::potential_finish_kernel, 1);
+  return sym_launch(c, k, 1, blocks, dyn_lds, a, rmb::PairConsts{}, rmb::potential_finish_kernel, 1);
 }
 
 struct ProposeArgs {
@@ -119,6 +130,21 @@ int rmb_blob_potential(rmb_ctx* c, double eps, double b, double eps_wall, double
   RMB_HIP(hipSetDevice(c->device));
   if (int rc = c->out.reserve(2 * sizeof(double))) return rc;
   if (int rc = rmbi::potential_device_impl(c, eps, b, eps_wall, b_wall, weight, blob_radius, form, (double*)c->out.p)) return rc;
+  RMB_HIP(hipMemcpyAsync(out, c->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  RMB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int rmb_blob_potential_table_device(rmb_ctx* c, double eps_wall, double b_wall, double weight, double blob_radius, int form, double* out_dev) {
+  return rmbi::potential_device_impl(c, 0.0, 1.0, eps_wall, b_wall, weight, blob_radius, form, out_dev, false, true);
+}
+
+int rmb_blob_potential_table(rmb_ctx* c, double eps_wall, double b_wall, double weight, double blob_radius, int form, double* out) {
+  if (int rc = rmbi::check_ready(c)) return rc;
+  if (!out) return fail(RMB_ERR_ARG, "null output pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  if (int rc = c->out.reserve(2 * sizeof(double))) return rc;
+  if (int rc = rmb_blob_potential_table_device(c, eps_wall, b_wall, weight, blob_radius, form, (double*)c->out.p)) return rc;
   RMB_HIP(hipMemcpyAsync(out, c->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   RMB_HIP(hipStreamSynchronize(c->stream));
   return 0;

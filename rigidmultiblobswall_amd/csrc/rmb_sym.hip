@@ -348,11 +348,19 @@ int pair_once_resident(rmb_ctx* c, const PairOnceErrors& msg, long n_min, bool r
 // Symmetric pair-force sweep (sym_force_kernels.h: each unordered pair once, F_ji = -F_ij) of pair shard `shard` of
 // `nshards` into a full-length result; atomic flushes.  Tile culling and the fp32 twin as the options say.
 // `law`: the blob-blob contact law, or the body-body Yukawa law on the resident points (FORCE_LAW_BODY: fp64 only, no
-// contact distance -- blob_radius and radii are not read).
+// contact distance -- blob_radius and radii are not read), or the context's tabulated law on them (FORCE_LAW_TABLE: the
+// same, eps and b are not read either; reach r_cut, records staged in tab_k * 32 bytes of dynamic LDS).
+rmb::PairTableRef pair_table_ref(const rmb_ctx* c) {
+  const double rc = pair_table_rcut(c);
+  return rmb::PairTableRef{(const double4*)c->pair_table.p, (int)c->tab_k, c->tab_r0, 1.0 / c->tab_h, (double)c->tab_k, rc * rc};
+}
+
 int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, double* out, const double* radii, long shard,
                      long nshards, ForceLaw law) {
+  const bool table = law == FORCE_LAW_TABLE;
   const bool body = law == FORCE_LAW_BODY;
-  if (body) { blob_radius = 0.0; radii = nullptr; }
+  if (body || table) { blob_radius = 0.0; radii = nullptr; }
+  if (table) { eps = 0.0; b = 1.0; }
   const SymConf cf = conf_of(c);
   const bool periodic = is_periodic(cf);
   const long n = c->n, tiles = (n + 63) / 64;
@@ -368,9 +376,10 @@ int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, doubl
   a.eps = eps; a.eps_over_b = eps / b; a.inv_b = 1.0 / b; a.two_a = 2.0 * blob_radius;
   a.ec = exp_consts();
   a.radii = radii;
+  a.tab = table ? pair_table_ref(c) : rmb::PairTableRef{};
   // "precision" = 32, open boundaries: the single-precision kernel -- the arithmetic of the reference's own GPU force
   // kernel (forces_pycuda.py:14-21)
-  const bool f32 = !body && (c->opt_force_precision ? c->opt_force_precision : c->opt_precision) == 32 && !periodic;
+  const bool f32 = !body && !table && (c->opt_force_precision ? c->opt_force_precision : c->opt_precision) == 32 && !periodic;
   // Tile culling: the force has the range of its exponential.  exp(-(r - 2a)/b) is exactly 0 in double precision
   // beyond (r - 2a)/b = 745.2 (750 here; 110 for the float kernel), so a tile pair whose bounding boxes are further
   // apart contributes nothing, bit for bit.  In a 262 144-roller monolayer that is 99 % of the tile pairs -- the
@@ -389,17 +398,20 @@ int sym_force_device(rmb_ctx* c, double eps, double b, double blob_radius, doubl
     }
     use_tile_bounds(c, a);
     const double reach = 2.0 * blob_radius + (f32 ? 110.0 : 750.0) * b;
-    a.cull2 = reach * reach;
+    a.cull2 = table ? a.tab.rcut2 : reach * reach;      // the table is exactly zero from r_cut on
   }
   typedef rmb::SymForceArgs A;
-  const SymKernel k = body ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false, rmb::BodyYukawaLaw>>(0)
+  const size_t dyn_lds = table ? (size_t)c->tab_k * sizeof(double4) : 0;
+  const SymKernel k = table ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false, rmb::TableLaw>>(0)
+                                        : sym_kernel_of<A, rmb::sym_force_kernel<false, false, rmb::TableLaw>>(0))
+                      : body ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false, rmb::BodyYukawaLaw>>(0)
                                        : sym_kernel_of<A, rmb::sym_force_kernel<false, false, rmb::BodyYukawaLaw>>(0))
                       : f32 ? sym_force32(radii != nullptr)
                           : radii ? (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, true>>(0) : sym_kernel_of<A, rmb::sym_force_kernel<false, true>>(0))
                                   : (periodic ? sym_kernel_of<A, rmb::sym_force_kernel<true, false>>(0) : sym_kernel_of<A, rmb::sym_force_kernel<false, false>>(0));
   long blocks;
-  plan_cull_sweep(c, k, a.step_end - a.step_begin, &blocks, &a.chunk_steps);
-  return sym_launch(c, k, 1, blocks, 0, a, rmb::PairConsts{}, rmb::sym_force_finalize_kernel, (n + 255) / 256);
+  plan_cull_sweep(c, k, a.step_end - a.step_begin, &blocks, &a.chunk_steps, 0, dyn_lds);
+  return sym_launch(c, k, 1, blocks, dyn_lds, a, rmb::PairConsts{}, rmb::sym_force_finalize_kernel, (n + 255) / 256);
 }
 
 }  // namespace rmbi

@@ -3,9 +3,11 @@
 // F_ij = -F_ji, so each unordered pair is evaluated once (one rsqrt + one exp) and applied with opposite signs.  Same
 // tile-pair rotation, LDS accumulation and static step schedule (sym_schedule.h) as sym_kernel; tile culling by the
 // range of the exponential.  The pair law is a policy of the one frame: BlobContactLaw (multi_bodies/forces_numba.py:12-55
-// semantics) or BodyYukawaLaw (multi_bodies_functions.py:359-384, a Yukawa repulsion between body locations).
+// semantics), BodyYukawaLaw (multi_bodies_functions.py:359-384, a Yukawa repulsion between body locations) or TableLaw (a
+// radial law the user supplies as a table of cubics, pair_table_kernels.h).
 #pragma once
 #include "pair_ops.h"
+#include "pair_table_kernels.h"
 #include "sym_schedule.h"
 
 namespace rmb {
@@ -34,9 +36,11 @@ struct SymForceArgs {
   // sorted slot s; the finalize kernel writes slot s to out[perm[s]].  nullptr = the caller's order.
   const unsigned* perm;
   double eps;           // BodyYukawaLaw: the strength itself (eps_over_b serves both laws)
+  PairTableRef tab;     // TableLaw: the context's pair table; cull2 is its r_cut^2
 };
 
-// Pair laws: f0 with (force ON i) = f0 dr, dr = r_j - r_i; r = |dr| and ir = 1/r come from the frame (one rsqrt per pair).
+// Pair laws: f0 with (force ON i) = f0 dr, dr = r_j - r_i; r2 = |dr|^2, r = |dr| and ir = 1/r come from the frame (one rsqrt
+// per pair).  STAGED: the law keeps a table in the workgroup's dynamic LDS, which the kernel stages before the walk begins.
 // Padding lanes sit 2e100 apart from everything: exp_nonpositive returns exactly 0 there, and so does every law.
 //
 // Blob-blob contact law, two_a = contact distance of the pair:
@@ -44,7 +48,8 @@ struct SymForceArgs {
 // Branch-free: x = min((2a - r)/b, 0) is 0 exactly for r <= 2a (and for r = NaN at coincident points, fmin keeps
 // the number), exp(0) = 1 exactly, and min(1/r, 1e25) = 1/r for every r > 2a -- one expression serves both ranges.
 struct BlobContactLaw {
-  static __device__ __forceinline__ double f0(const SymForceArgs& a, double two_a, double r, double ir) {
+  static constexpr bool STAGED = false;
+  static __device__ __forceinline__ double f0(const SymForceArgs& a, double two_a, double, double r, double ir) {
     const double x = fmin((two_a - r) * a.inv_b, 0.0);
     const double e = exp_nonpositive(a.ec, x);
     // the multiplier first, the exponential last: beyond (r - 2a)/b = 708 e is a denormal, and e min(1/r, 1e25) would be
@@ -59,9 +64,20 @@ struct BlobContactLaw {
 // reference; here ir is not finite then, fmin keeps the exponent a number, and the two bodies of that pair -- no
 // others -- get non-finite sums.
 struct BodyYukawaLaw {
-  static __device__ __forceinline__ double f0(const SymForceArgs& a, double, double r, double ir) {
+  static constexpr bool STAGED = false;
+  static __device__ __forceinline__ double f0(const SymForceArgs& a, double, double, double r, double ir) {
     const double e = exp_nonpositive(a.ec, fmin(-r * a.inv_b, 0.0));
     return -((__builtin_fma(a.eps, ir, a.eps_over_b) * (ir * ir)) * e);      // the denormal e last, as above
+  }
+};
+
+// Tabulated radial law U(r) (pair_table_kernels.h): F_on_i = (U'(r)/r) dr, f0 = U'(r) min(1/r, 1e25) as the contact law's
+// near branch, so coincident blobs (dr = 0, r = NaN) give a zero force; +0.0 exactly from r_cut on (padding included).
+// No contact distance (two_a is unused), no exponential.
+struct TableLaw {
+  static constexpr bool STAGED = true;
+  static __device__ __forceinline__ double f0(const SymForceArgs& a, double, double r2, double r, double ir) {
+    return pair_table_f0(a.tab, r2, r, ir);
   }
 };
 
@@ -78,7 +94,7 @@ __device__ __forceinline__ void pair_force(const SymForceArgs& a, double two_a, 
   const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
   const double ir = rsqrt_f64(r2);
   const double r = r2 * ir;
-  const double f0 = LAW::f0(a, two_a, r, ir);
+  const double f0 = LAW::f0(a, two_a, r2, r, ir);
   fx = f0 * dx; fy = f0 * dy; fz = f0 * dz;
 }
 
@@ -90,6 +106,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForc
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double4* rec = rec_all[wave];
   double* accj = accj_all[wave];
+  if constexpr (LAW::STAGED) stage_pair_table(a.tab);      // once per workgroup, before any wave starts its walk
   const long n_waves = (long)gridDim.x * kSymWaves;
   const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
   const long s_total = a.step_end - a.step_begin;

@@ -14,6 +14,11 @@ context the deck is refused.  Rigid decks follow the reference's driver (force_t
 term, :443).  The reference's roller integrator builds its forces from calc_one_blob_forces + calc_blob_blob_forces alone
 (quaternion_integrator_rollers.py:930-933) and never evaluates the option; a roller deck here adds the law the option
 names to every force evaluation, which is that integrator with the law in its pair-force hook.
+
+`blob_blob_force_implementation table_hip` with `blob_blob_pair_table FILE` is this engine's own spelling: the blob-blob
+law is the radial table in FILE (pair_table.py; rows `r U dU/dr`, path relative to the deck) instead of the contact
+exponential.  Refused when the file is missing and, like the body-body forces, on a context without the sweep
+(validate(..., pair_tables=...)).
 """
 import numpy as np
 
@@ -51,7 +56,7 @@ def hydrodynamic_mode(impl, option, free_surface=False):
   raise ValueError("%s %r: unknown implementation suffix %r" % (option, impl, suffix))
 
 
-def validate(read, uses_dense_blocks=True, body_body_forces=False):
+def validate(read, uses_dense_blocks=True, body_body_forces=False, pair_tables=None):
   """Checks every implementation option of a ReadInput deck against `domain`; returns the hydrodynamic mode
   ('single_wall', 'no_wall' or 'in_plane' as given by `domain`, or 'free_surface': a rigid deck whose product is a
   `<backend>_free_surface` one under `domain single_wall`, multi_bodies.py:262-265).
@@ -66,7 +71,11 @@ def validate(read, uses_dense_blocks=True, body_body_forces=False):
   `<backend>_free_surface` product and returns 'free_surface'; rigid decks keep the reference's spelling.
 
   body_body_forces: the caller's context serves the body-body force sweep (hasattr(ctx, "body_body_force_device"));
-  without it a deck with `body_body_force_torque_implementation` other than `None` is refused."""
+  without it a deck with `body_body_force_torque_implementation` other than `None` is refused.
+  pair_tables: the same for `blob_blob_force_implementation table_hip` (hasattr(ctx, "pair_table_force_device"); None: as
+  body_body_forces -- both sweeps live on a single-GPU MobilityContext)."""
+  if pair_tables is None:
+    pair_tables = body_body_forces
   domain = read.domain
   if domain == "free_surface":
     if uses_dense_blocks:
@@ -77,7 +86,7 @@ def validate(read, uses_dense_blocks=True, body_body_forces=False):
     if "radii" in impl or _split(impl)[0] is None or _split(impl)[1] != "free_surface":
       raise ValueError("mobility_vector_prod_implementation %r: `domain free_surface` needs a <backend>_free_surface "
                        "product" % (impl,))
-    _check_forces(read, body_body_forces)
+    _check_forces(read, body_body_forces, pair_tables)
     return "free_surface"
   if domain not in ("single_wall", "no_wall", "in_plane"):
     raise ValueError("domain %r: expected single_wall, no_wall or in_plane" % (domain,))
@@ -111,13 +120,44 @@ def validate(read, uses_dense_blocks=True, body_body_forces=False):
       raise ValueError("%s %r is a %s implementation but the deck says `domain %s`: the reference would mix an unbounded "
                        "mobility with wall checks (or the reverse); state the intended one"
                        % (option, getattr(read, option), mode, domain))
-  _check_forces(read, body_body_forces)
+  _check_forces(read, body_body_forces, pair_tables)
   return domain
 
 
-def _check_forces(read, body_body_forces=False):
+def pair_table_path(read):
+  """The file of a `blob_blob_force_implementation table_hip` deck (`blob_blob_pair_table FILE`, relative to the deck), or a
+  ValueError: keyword missing, file missing, or the keyword without the implementation string."""
+  import os
+  ff, name = read.blob_blob_force_implementation, getattr(read, "blob_blob_pair_table", None)
+  if ff != "table_hip":
+    if name is not None:
+      raise ValueError("blob_blob_pair_table %r is read by `blob_blob_force_implementation table_hip` only; the deck says %r" % (name, ff))
+    return None
+  if name is None:
+    raise ValueError("blob_blob_force_implementation table_hip needs `blob_blob_pair_table FILE` (text, rows `r U dU/dr` on a uniform grid)")
+  path = read.resolve(name)
+  if not os.path.isfile(path):
+    raise ValueError("blob_blob_pair_table %r: no such file (looked for %s)" % (name, path))
+  return path
+
+
+def pair_table(read):
+  """The PairTable of a `table_hip` deck, or None."""
+  path = pair_table_path(read)
+  if path is None:
+    return None
+  from .pair_table import PairTable
+  return PairTable.load(path)
+
+
+def _check_forces(read, body_body_forces=False, pair_tables=False):
   """The force options of a deck the time steppers can honour, or a ValueError."""
   ff = read.blob_blob_force_implementation
+  if pair_table_path(read) is not None:       # table_hip: a user-defined radial law (pair_table.py)
+    if not pair_tables:
+      raise ValueError("blob_blob_force_implementation table_hip: a pair table runs on a single-GPU MobilityContext; this "
+                       "context does not serve the sweep (no pair shards, no multi-device engine)")
+    ff = "hip"
   if "radii" in ff:
     raise ValueError("blob_blob_force_implementation %r needs per-blob radii; the time steppers assume one blob radius "
                      "(dispatch.set_blob_blob_forces serves the product)" % (ff,))

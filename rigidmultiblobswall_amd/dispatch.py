@@ -59,6 +59,24 @@ def set_blob_blob_forces(implementation, accept_reference_gpu_names=False, *args
   table = {"None": _zero_forces, "hip": _forces.calc_blob_blob_forces_hip, "tree_hip": _forces.calc_blob_blob_forces_tree_hip}
   if accept_reference_gpu_names:
     table["pycuda"] = table["hip"]
+  if implementation == "table_hip":
+    # a user-defined radial law as a table (pair_table.py): pair_table= a PairTable, or pair_table_file= its text file
+    import os
+    from functools import partial
+    from .pair_table import PairTable
+    T = kwargs.get("pair_table")
+    if T is None:
+      path = kwargs.get("pair_table_file")
+      if path is None:
+        raise ValueError("blob_blob_force_implementation table_hip needs pair_table= (a PairTable) or pair_table_file=")
+      if not os.path.isfile(path):
+        raise ValueError("blob_blob_force_implementation table_hip: pair table file %r does not exist" % (path,))
+      T = PairTable.load(path)
+    if not isinstance(T, PairTable):
+      raise ValueError("blob_blob_force_implementation table_hip: pair_table= must be a PairTable, got %r" % (type(T).__name__,))
+    if len(_mob.devices()) > 1:
+      raise ValueError("blob_blob_force_implementation table_hip runs on one device; %d are configured (mobility.set_devices)" % len(_mob.devices()))
+    return partial(_forces.calc_blob_blob_forces_table_hip, pair_table=T)
   if implementation == "radii_hip":
     # one radius per blob (multi_bodies_functions.py:270-277)
     from functools import partial

@@ -82,6 +82,25 @@ def calc_blob_blob_forces_radii_hip(r_vectors, radius_blobs, *args, **kwargs):
   return ctx.blob_blob_force_radii(radius_blobs, kwargs.get('repulsion_strength'), kwargs.get('debye_length'))
 
 
+def calc_blob_blob_forces_table_hip(r_vectors, *args, **kwargs):
+  """Blob-blob forces of a user-defined radial law: pair_table= a PairTable (pair_table.py), periodic_length= as above.
+  One symmetric fp64 sweep on one device; repulsion_strength, debye_length and blob_radius are not read (the table is the
+  whole law).  Per-blob radii, single precision and the multi-device engine do not serve a table."""
+  from .pair_table import PairTable
+  table = kwargs.get('pair_table')
+  if not isinstance(table, PairTable):
+    raise ValueError("calc_blob_blob_forces_table_hip needs pair_table= a PairTable, got %r" % (type(table).__name__,))
+  if kwargs.get('radius_blobs') is not None:
+    raise ValueError("a pair table is one law for every pair: per-blob radii are not served")
+  L = kwargs.get('periodic_length')
+  if L is None:
+    L = np.zeros(3)
+  ctx = _context(0)      # a table lives in one single-device context
+  ctx.set_positions(r_vectors, 1.0, L, wall=False)
+  ctx._use_pair_table(table)
+  return ctx.pair_table_force()
+
+
 def calc_body_body_forces_torques_hip(bodies, r_vectors, *args, **kwargs):
   """`calc_body_body_forces_torques_python` (multi_bodies_functions.py:387-408) on the device: a Yukawa repulsion between
   the bodies' `location`s, one symmetric fp64 sweep over the N_b centres instead of the Python double loop.  Returns

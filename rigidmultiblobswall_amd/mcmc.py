@@ -2,6 +2,7 @@
 
     python -m rigidmultiblobswall_amd.mcmc [inputfile] [--device N] [--potential soft|yukawa] [--rng reference|batched]
                                            [--moves all|single] [--body-potential none|deck|EPS,B] [--gr RMAX,BINS]
+                                           [--pair-table FILE]
 
 Same decks, same outputs (.inputfile, .random_state, .clones per saved step or one appended .config, .time, .MCMC_info)
 and, with rng="reference", the same chain as the reference script for the same seed: the draws come from a
@@ -69,7 +70,8 @@ def refuse_user_defined_potential(directory="."):
     raise UserDefinedPotentialError(
         "%s found: CUDA-string potentials are not supported by the HIP sampler.  The Yukawa potential of the reference's "
         "boomerang_suspension example is built in: run with --potential yukawa (MCMCSampler(potential='yukawa')) from a "
-        "directory without that file; any other user-defined potential is not implemented." % path)
+        "directory without that file; any other radial pair potential runs as a table: --pair-table FILE "
+        "(MCMCSampler(pair_table=PairTable...), pair_table.py); any other user-defined potential is not implemented." % path)
 
 
 def body_length(reference_configuration, blob_radius):
@@ -259,7 +261,7 @@ class _DeviceState(object):
       self.ctx.set_positions(self.r_new, s.blob_radius, s.periodic_length, wall=False)
       return self.ctx.blob_potential_device(s.repulsion_strength, s.debye_length, s.blob_radius,
                                             repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
-                                            weight=s.weight, potential=s.potential, out=out)
+                                            weight=s.weight, potential=s.potential, out=out, pair_table=s.pair_table)
 
   def _body_energy(self, loc, out):
     """U_body of the locations `loc` into out (one entry): the energy sweep on the second context."""
@@ -298,7 +300,7 @@ class _DeviceState(object):
       self.ctx.set_positions(self.r_new, s.blob_radius, s.periodic_length, wall=False)
       u_one, u_pair = self.ctx.blob_potential(s.repulsion_strength, s.debye_length, s.blob_radius,
                                               repulsion_strength_wall=s.repulsion_strength_wall, debye_length_wall=s.debye_length_wall,
-                                              weight=s.weight, potential=s.potential)
+                                              weight=s.weight, potential=s.potential, pair_table=s.pair_table)
     if self.law is not None:      # of the proposed locations (current_energy proposes the current ones)
       return u_one + u_pair + float(self._body_energy(self.loc_new, self.u_body).item())
     return u_one + u_pair
@@ -354,7 +356,7 @@ class MCMCSampler(object):
   (running energy, recomputed full energy) of every save."""
 
   def __init__(self, read, device=0, potential="soft", rng="reference", energy=None, write_files=True, verbose=False,
-               check_user_potential=True, keep_saved=None, moves="all", body_potential=None, gr=None):
+               check_user_potential=True, keep_saved=None, moves="all", body_potential=None, gr=None, pair_table=None):
     if check_user_potential:
       refuse_user_defined_potential(".")
     if potential not in ("soft", "yukawa"):
@@ -366,6 +368,20 @@ class MCMCSampler(object):
     if moves == "single" and energy is None and not isinstance(device, (int, np.integer)):
       raise ValueError("moves='single' takes a device index, not %r" % (device,))
     self.moves = moves
+    # a user-defined radial pair law (pair_table.PairTable, or the path of its file): replaces the pair term of `potential`,
+    # whose one-blob form stays; moves="all" only
+    if isinstance(pair_table, str):
+      from .pair_table import PairTable
+      pair_table = PairTable.load(pair_table)
+    if pair_table is not None:
+      from .pair_table import PairTable
+      if not isinstance(pair_table, PairTable):
+        raise ValueError("pair_table must be a PairTable or the path of its file, got %r" % (type(pair_table).__name__,))
+      if moves == "single":
+        raise ValueError("moves='single' does not serve a pair table: the single-body energy difference has no table variant; use moves='all'")
+      if energy is not None:
+        raise ValueError("pair_table goes with the HIP energy; a caller's energy= function is the whole potential")
+    self.pair_table = pair_table
     self.gr = None
     if gr is not None:
       try:
@@ -602,6 +618,9 @@ def main(argv=None):
   ap.add_argument("--body-potential", default="none", metavar="none|deck|EPS,B",
                   help="Yukawa repulsion between body locations: none (the reference), deck (the steppers' law for this deck: "
                        "repulsion_strength, debye_length; needs body_body_force_torque_implementation python|hip) or two numbers")
+  ap.add_argument("--pair-table", default=None, metavar="FILE",
+                  help="a radial pair potential as a table (text: r U dU/dr on a uniform grid) instead of the pair term of --potential; "
+                       "--moves all only")
   ap.add_argument("--gr", default=None, metavar="RMAX,BINS",
                   help="accumulate the pair-distance histogram of the body locations at every saved step and write <output_name>.gr.dat")
   args = ap.parse_args(argv)
@@ -619,7 +638,7 @@ def main(argv=None):
     except ValueError:
       ap.error("--body-potential takes none, deck or EPS,B (two numbers), got %r" % (args.body_potential,))
   sampler = MCMCSampler(args.inputfile, device=args.device, potential=args.potential, rng=args.rng, verbose=True, moves=args.moves,
-                        body_potential=body_potential, gr=gr)
+                        body_potential=body_potential, gr=gr, pair_table=args.pair_table)
   try:
     sampler.run()
   finally:

@@ -10,7 +10,10 @@ every call) behind the same calls and keyword names:
   compute_total_energy_hip(bodies, r_vectors, **kwargs)  -> U_blobs + U_bodies
 and, beyond the reference, the energy difference of ONE moved body in O(n_body N) (the single-body moves of mcmc.py):
   body_energy_difference_hip(r_vectors, first, body_new, **kwargs) -> (dU_one_blob, dU_pair)
-`potential="soft"|"yukawa"` is the one extra keyword: the module's own form, or the Yukawa form of the reference's only
+`pair_table=T` (a PairTable, pair_table.py) replaces the blob-blob pair term by a user-defined radial law in
+blobs_potential_hip / compute_total_energy_hip (bodies_potential_hip passes it by: a table is a blob-blob law, there are no
+body-body tables); body_energy_difference_hip refuses it (single-body moves do not serve a table).
+`potential="soft"|"yukawa"` is the other extra keyword: the module's own form, or the Yukawa form of the reference's only
 MCMC example (examples/boomerang_suspension/potential_pycuda_user_defined.py).  A reference checkout binds it with
   import rigidmultiblobswall_amd.potential as p; many_body_potential_pycuda.compute_total_energy = p.compute_total_energy_hip
 """
@@ -46,7 +49,7 @@ def potential_terms(ctx, **kwargs):
   return ctx.blob_potential(kwargs.get('repulsion_strength'), kwargs.get('debye_length'), kwargs.get('blob_radius'),
                             repulsion_strength_wall=kwargs.get('repulsion_strength_wall') or 0.0,
                             debye_length_wall=kwargs.get('debye_length_wall') or 1.0, weight=kwargs.get('weight') or 0.0,
-                            potential=kwargs.get('potential', 'soft'))
+                            potential=kwargs.get('potential', 'soft'), pair_table=kwargs.get('pair_table'))
 
 
 def blobs_potential_hip(r_vectors, *args, **kwargs):
@@ -67,6 +70,8 @@ def body_energy_difference_hip(r_vectors, first, body_new, *args, **kwargs):
   replaced by body_new: the touched terms only, each subtracted before it is accumulated (rmb_mcmc_body_delta_device).
   r_vectors / body_new: numpy arrays or CUDA float64 tensors; same keyword arguments as blobs_potential_hip."""
   import torch
+  if kwargs.get('pair_table') is not None:
+    raise ValueError("the single-body energy difference does not serve a pair table (pair_table=): use the whole-configuration energy")
   if kwargs.get('potential', 'soft') not in POTENTIAL_FORMS:
     raise ValueError("potential must be 'soft' or 'yukawa'")
   ctx = _context()

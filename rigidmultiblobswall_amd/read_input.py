@@ -41,6 +41,7 @@ _OPTIONS = {
     "debye_length": ("debye_length", float, 1.0),
     "blob_blob_force_implementation": ("blob_blob_force_implementation", str, "None"),
     "body_body_force_torque_implementation": ("body_body_force_torque_implementation", str, "None"),
+    "blob_blob_pair_table": ("blob_blob_pair_table", str, None),      # this engine's own: file of `blob_blob_force_implementation table_hip`
     "save_body_mobility": ("save_body_mobility", str, "False"),
     "save_blobs_mobility": ("save_blobs_mobility", str, "False"),
     "save_velocities": ("save_velocities", str, "False"),

@@ -144,6 +144,9 @@ class RigidIntegrator(object):
     # body-body forces (multi_bodies_functions.py:359-408): None, or (repulsion_strength, debye_length) of the Yukawa
     # repulsion between body locations -- one more symmetric sweep, over the nb centres
     self.body_body_force = None
+    # a user-defined radial pair law (pair_table.PairTable) or None; when set it REPLACES the contact law of the blob-blob
+    # step (repulsion_strength / debye_length are not read), it is not added to it
+    self.blob_pair_table = None
     # hooks, as the reference's attributes of the same names (tensors in / out)
     self.calc_slip = None                       # callable(integrator) -> (Nblobs, 3) tensor
     self.slip_body_frame = None                 # (Nblobs, 3) tensor: constant active slip in the body frame (.slip files)
@@ -241,7 +244,11 @@ class RigidIntegrator(object):
     if helper is not None and helper is self.susp.ctx and r.is_contiguous() and r.dtype == torch.float64:
       # two launches: the pair repulsion, then weight + wall repulsion added to its z entries (rmb_one_blob_force_device)
       f = None
-      if self.repulsion_strength != 0.0:
+      if self.blob_pair_table is not None:
+        helper.set_positions(r.view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
+        f = self._pair_table_forces(helper)
+        helper.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
+      elif self.repulsion_strength != 0.0:
         helper.set_positions(r.view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
         f = helper.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a)
         helper.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
@@ -253,12 +260,24 @@ class RigidIntegrator(object):
       h = r[:, 2]
       e = self.repulsion_strength_wall / self.debye_length_wall
       f[:, 2] += torch.where(h > self.a, e * torch.exp(-(h - self.a) / self.debye_length_wall), torch.full_like(h, e))
-    if self.repulsion_strength != 0.0:
+    if self.blob_pair_table is not None:
+      ctx = self.susp.ctx
+      ctx.set_positions(r.contiguous().view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
+      f = f + self._pair_table_forces(ctx).view(-1, 3)
+      ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
+    elif self.repulsion_strength != 0.0:
       ctx = self.susp.ctx
       ctx.set_positions(r.contiguous().view(-1), self.a, self.periodic_length, False)   # true heights, no clamp
       f = f + ctx.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a).view(-1, 3)
       ctx.set_positions(self.susp.r_dev, self.a, self.periodic_length, self.susp.ctx_wall)  # back to the mobility view
     return f
+
+  def _pair_table_forces(self, ctx):
+    """3 N forces of `blob_pair_table` on ctx's resident raw positions."""
+    if not hasattr(ctx, "pair_table_force_device"):
+      raise ValueError("a pair table needs a single-GPU MobilityContext; %s does not serve the sweep" % type(ctx).__name__)
+    ctx._use_pair_table(self.blob_pair_table)
+    return ctx.pair_table_force_device()
 
   def _body_body_forces(self):
     """(nb, 3) Yukawa forces between the body locations of the bound configuration -- the one the blob forces of this
@@ -844,7 +863,8 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   from . import deck_modes
   # ValueError for modes this engine does not run; body-body forces only where the context has the sweep (a context made
   # here is a MobilityContext, which does)
-  domain = deck_modes.validate(read, uses_dense_blocks=True, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"))
+  domain = deck_modes.validate(read, uses_dense_blocks=True, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"),
+                               pair_tables=ctx is None or hasattr(ctx, "pair_table_force_device"))
   phoretic = deck_modes.phoretic(read)                  # ValueError for phoretic modes this engine does not run
   block_boundary = None
   if domain == "free_surface":
@@ -870,6 +890,7 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
     integ.debye_length = read.debye_length
   if read.body_body_force_torque_implementation != "None":     # the same two numbers, as the reference's kwargs
     integ.body_body_force = (read.repulsion_strength, read.debye_length)
+  integ.blob_pair_table = deck_modes.pair_table(read)      # `blob_blob_force_implementation table_hip`: replaces the contact law
   if any_slip:
     integ.slip_body_frame = torch.as_tensor(b["slips"], device=integ.device)
   if phoretic:

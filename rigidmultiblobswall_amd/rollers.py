@@ -90,6 +90,9 @@ class RollersIntegrator(object):
     # body-body forces (multi_bodies_functions.py:359-408): None, or (repulsion_strength, debye_length) of the Yukawa
     # repulsion between body locations -- the rollers themselves; added to the pair forces of every force evaluation
     self.body_body_force = None
+    # a user-defined radial pair law (pair_table.PairTable) or None; when set it REPLACES the contact law of the pair-force
+    # step (repulsion_strength / debye_length are not read), it is not added to it
+    self.blob_pair_table = None
     # replaceable hooks, as the reference's attributes of the same names; tensors (N,3) in and out
     self.calc_one_blob_forces = self._one_blob_forces
     self.calc_blob_blob_forces = self._blob_blob_forces
@@ -227,11 +230,16 @@ class RollersIntegrator(object):
   def _blob_blob_forces(self, r):
     """Pair forces at r: the blob-blob repulsion, plus the body-body Yukawa force (`body_body_force`; a roller is a body,
     its location the blob's) as a second sweep over the positions the first one made resident."""
-    if self.repulsion_strength == 0.0 and self.body_body_force is None:
+    if self.repulsion_strength == 0.0 and self.body_body_force is None and self.blob_pair_table is None:
       return torch.zeros_like(r)
     self._bind(r, wall=False)    # forces act on the true heights, not the clamped ones
     f = None
-    if self.repulsion_strength != 0.0:
+    if self.blob_pair_table is not None:
+      if not hasattr(self.ctx, "pair_table_force_device"):
+        raise ValueError("a pair table needs a single-GPU MobilityContext; %s does not serve the sweep" % type(self.ctx).__name__)
+      self.ctx._use_pair_table(self.blob_pair_table)
+      f = self.ctx.pair_table_force_device().view(-1, 3)
+    elif self.repulsion_strength != 0.0:
       f = self.ctx.blob_blob_force_device(self.repulsion_strength, self.debye_length, self.a).view(-1, 3)
     if self.body_body_force is not None:
       if not hasattr(self.ctx, "body_body_force_device"):
@@ -642,7 +650,8 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   from . import structures as st
   # ValueError for modes this engine does not run; body-body forces only where the context has the sweep (a context made
   # here is a MobilityContext, which does)
-  domain = deck_modes.validate(read, uses_dense_blocks=False, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"))
+  domain = deck_modes.validate(read, uses_dense_blocks=False, body_body_forces=ctx is None or hasattr(ctx, "body_body_force_device"),
+                               pair_tables=ctx is None or hasattr(ctx, "pair_table_force_device"))
   deck_modes.phoretic(read)                             # ValueError for .Laplace files
   locations = []
   body_types = []
@@ -670,6 +679,7 @@ def integrator_from_input(read, device="cuda:0", ctx=None, rng=None):
   if read.blob_blob_force_implementation != "None":
     integ.repulsion_strength = read.repulsion_strength
     integ.debye_length = read.debye_length
+  integ.blob_pair_table = deck_modes.pair_table(read)      # `blob_blob_force_implementation table_hip`: replaces the contact law
   if read.body_body_force_torque_implementation != "None":     # the same two numbers, as the reference's kwargs
     integ.body_body_force = (read.repulsion_strength, read.debye_length)
   integ.periodic_length = np.asarray(read.periodic_length, dtype=np.float64)
