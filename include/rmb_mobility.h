@@ -558,6 +558,36 @@ int rmb_van_hove_self_frames_device(rmb_ctx* ctx, const double* frames_dev, long
                                     int plane, double r_max, long n_bins, unsigned long long* hist_dev, double* moments_dev_or_null);
 int rmb_van_hove_distinct_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, long n_lags,
                                         long o_begin, long o_end, int plane, double r_max, long n_bins, unsigned long long* hist_dev);
+/* Bond-orientational order of point frames (bond_order_kernels.h; bondorder.py): the sums behind psi_m(i), g_m(r), C_m(t).
+ * frames = (n_frames, n, 3) packed doubles on the device, possibly unwrapped; L = 3 periods on the host (<= 0: open); every
+ * separation in the minimal image of every direction with a positive period (rmb_pair_histogram's formula).  plane = 1 (xy):
+ * distances are in-plane, sqrt(dx^2 + dy^2); plane = 0 (xyz): three-dimensional.  The bond angle is always the in-plane one.
+ *   rmb_bond_order_frames_device   out[f, i] = {N_i, Re sum_j z_ij^m1, Im sum_j z_ij^m1, ...} over the neighbours j of point i
+ *                                  in frame f: d_ij^2 < r_cut^2 and rho_ij^2 = dx^2 + dy^2 > 0 (the point itself and points
+ *                                  stacked on it have no angle: out of the sums and of the count), z = (dx + i dy) / rho.
+ *                                  out = (n_frames, n, 1 + 2 n_orders) doubles, OVERWRITTEN; N_i is exact.  orders: n_orders
+ *                                  (1 ... 4) values 1 ... 16 on the host.  No trigonometric function: one reciprocal square
+ *                                  root and binary powering.  Atomic-free, fixed-order sums: the same call gives the same
+ *                                  bits.  source_chunk = 0: the sources of a frame are chunked as planned; > 0: that many
+ *                                  sources per chunk (rounded up to a multiple of 4; the chunk count may change the last bits).
+ *                                  psi_m(i) = sum / N_i is the caller's division.  r_cut should not exceed half the smallest
+ *                                  positive period (beyond it a neighbour is met through one image only).
+ *   rmb_pair_field_frames_device   field = (n_frames, n, 2) int32 on the device, (a, b) = rint(psi 2^30) with |a|, |b| <= 2^30.
+ *                                  For every unordered pair of a frame with r < r_max, binned as rmb_pair_histogram:
+ *                                  counts[bin] += 1 and sums[bin] += (a_i a_j + b_i b_j + 2^29) >> 30 (int64, arithmetic
+ *                                  shift).  counts = [n_bins] unsigned 64-bit, sums = [n_bins] signed 64-bit, both ADDED to:
+ *                                  integer accumulators in LDS, integer atomics, the same bits for every launch plan and
+ *                                  point order.  g_m(r_b) = sums_b / (2^30 counts_b), within (sqrt(2) + 1/2) 2^-30 of the
+ *                                  unquantised mean.
+ * Always fp64 positions, single device, asynchronous on the context's stream.  Nothing of the resident configuration is read or
+ * written (only the context's device, stream, and the one-sided sweeps' workspace of chunk partials for the first entry).
+ * RMB_ERR_ARG, before the context or the device is touched: a null pointer, negative sizes, plane not 0 or 1, r_cut / r_max not
+ * positive and finite, n_orders outside 1 ... 4, an order outside 1 ... 16, source_chunk < 0, n_bins outside 1 ... 4096, more
+ * pairs than one launch can step through.  n_frames = 0 and n = 0 (for the second entry also n = 1) leave the outputs unchanged. */
+int rmb_bond_order_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, const double* L, double r_cut, int plane,
+                                 const int* orders, int n_orders, long source_chunk, double* out_dev);
+int rmb_pair_field_frames_device(rmb_ctx* ctx, const double* frames_dev, const int* field_dev, long n_frames, long n, const double* L,
+                                 int plane, double r_max, long n_bins, unsigned long long* counts_dev, long long* sums_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

@@ -22,6 +22,7 @@ callers built on the path, each mirroring the reference module of th
   correlation.py       RadialDistribution: g(r) from the HIP pair-distance histogram, python -m rigidmultiblobswall_amd.correlation
   msd.py               MeanSquareDisplacement: 6 x 6 translational-rotational MSD from the HIP lag sweep, python -m rigidmultiblobswall_amd.msd
   scattering.py        IntermediateScattering: S(k), F(k, t), F_s(k, t) from the HIP Fourier sweeps, python -m rigidmultiblobswall_amd.scattering
+  bondorder.py         BondOrder: psi_m, g_m(r), C_m(t) from the HIP neighbour and pair-field sweeps, python -m rigidmultiblobswall_amd.bondorder
 """
 from . import _lib  # noqa: F401
 from .context import MobilityContext  # noqa: F401

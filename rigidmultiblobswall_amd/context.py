@@ -775,6 +775,56 @@ class MobilityContext(object):
                                                              ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
     return out
 
+  def bond_order_frames_device(self, frames, periodic_length, r_cut, orders=(6,), plane="xy", out=None, source_chunk=0):
+    """Neighbour sums behind the bond-orientational order psi_m(i) of `frames`, a contiguous CUDA float64 tensor (n_frames, n, 3),
+    possibly unwrapped (rmb_bond_order_frames_device).  The neighbours of point i are the j with d_ij < r_cut -- in the minimal
+    image of every direction with a positive period (periodic_length: three periods, <= 0: open), d the in-plane distance under
+    plane="xy" and the 3-D one under "xyz" -- and rho_ij > 0 (a point stacked on i has no bond angle).  orders: 1 ... 4 values m
+    in 1 ... 16.  Returns a CUDA float64 tensor (n_frames, n, 1 + 2 K) of [N_i, Re sum z^m1, Im sum z^m1, ...], z = (dx + i dy) /
+    rho; out= (that shape, contiguous) is OVERWRITTEN.  psi_m(i) = sum / N_i.  source_chunk: sources per chunk of the sweep, 0 =
+    planned.  Asynchronous on torch's stream; the resident configuration is neither read nor changed."""
+    n_frames, n = self._scattering_frames(frames)
+    L = _as_f64(periodic_length, 3)
+    if plane not in VAN_HOVE_PLANES:
+      raise ValueError("plane must be one of %s, got %r" % (sorted(VAN_HOVE_PLANES), plane))
+    m = np.asarray(orders).reshape(-1)
+    if m.dtype.kind not in "iu" or not 1 <= m.size <= 4 or np.any(m < 1) or np.any(m > 16):
+      raise ValueError("orders must be 1 ... 4 integers in 1 ... 16, got %r" % (orders,))
+    m = np.ascontiguousarray(m, dtype=np.int32)
+    K = int(m.size)
+    out = _cuda_out(out, (n_frames, n, 1 + 2 * K), "(n_frames, n, 1 + 2 K)", "float64", frames.device, zero=False)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_bond_order_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
+                                                      _ptr(L), float(r_cut), VAN_HOVE_PLANES[plane], ctypes.c_void_p(m.ctypes.data), K,
+                                                      int(source_chunk), ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
+
+  def pair_field_correlation_frames_device(self, frames, field, periodic_length, r_max, n_bins, plane="xy", counts=None, sums=None):
+    """Pair correlation of a quantised per-point field over the unordered pairs of every frame (rmb_pair_field_frames_device).
+    frames: contiguous CUDA float64 (n_frames, n, 3); field: contiguous CUDA int32 (n_frames, n, 2) of (a, b) = rint(psi 2^30),
+    |a|, |b| <= 2^30 (bondorder.quantise).  For every pair with r < r_max (plane and periodic_length as
+    bond_order_frames_device, binning as pair_histogram_frames_device): counts[bin] += 1, sums[bin] += (a_i a_j + b_i b_j +
+    2^29) >> 30.  Both are contiguous CUDA int64 tensors of n_bins entries, ADDED to (None: new tensors of zeros); n_bins <=
+    4096.  Returns (counts, sums): integer sums, the same bits for every point order and every cut of the trajectory.
+    Asynchronous on torch's stream; the resident configuration is neither read nor changed."""
+    import torch
+    n_frames, n = self._scattering_frames(frames)
+    if not (isinstance(field, torch.Tensor) and field.is_cuda and field.dtype == torch.int32 and field.is_contiguous() and tuple(field.shape) == (n_frames, n, 2)):
+      raise ValueError("field must be a contiguous CUDA int32 tensor of shape (n_frames, n, 2)")
+    L = _as_f64(periodic_length, 3)
+    if plane not in VAN_HOVE_PLANES:
+      raise ValueError("plane must be one of %s, got %r" % (sorted(VAN_HOVE_PLANES), plane))
+    n_bins = int(n_bins)
+    counts = _cuda_out(counts, (max(n_bins, 0),), "(n_bins,)", "int64", frames.device, what="counts")
+    sums = _cuda_out(sums, (max(n_bins, 0),), "(n_bins,)", "int64", frames.device, what="sums")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_pair_field_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None,
+                                                      ctypes.c_void_p(field.data_ptr()) if field.numel() else None, n_frames, n, _ptr(L),
+                                                      VAN_HOVE_PLANES[plane], float(r_max), n_bins,
+                                                      ctypes.c_void_p(counts.data_ptr()) if counts.numel() else None,
+                                                      ctypes.c_void_p(sums.data_ptr()) if sums.numel() else None))
+    return counts, sums
+
   @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""

@@ -36,6 +36,9 @@
 //   rmb_van_hove.hip  lag histograms behind the van Hove functions G_s(r, t), G_d(r, t) of caller-owned frames
 //                    (van_hove_kernels.h): self sweep (a lane owns a point; counts and the moments sum r^2, sum r^4, finishing
 //                    launch) and distinct sweep over ordered pairs (a workgroup owns a lag; the rotation of the pair-once frame)
+//   rmb_bond_order.hip  bond-orientational order of caller-owned frames (bond_order_kernels.h): the neighbour sums behind psi_m
+//                    (a policy of the one-sided frame, launched here with the frame as a grid dimension) and the pair correlation
+//                    of a quantised per-point field behind g_m(r) (a policy of the pair-once frame, integer accumulators)
 //   pair_table_kernels.h (a header) the tabulated radial pair law: what TableLaw of the force sweep (rmb_sym.hip) and the TABLE
 //                    instances of the energy sweep (rmb_potential.hip) share -- LDS staging, interval lookup, the two cubics;
 //                    rmb_ctx_set_pair_table and the force entry points are in rmb_entry.hip
