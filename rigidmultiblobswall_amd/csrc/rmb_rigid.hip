@@ -68,7 +68,9 @@ __global__ __launch_bounds__(256) void rigid_advance_kernel(const AdvanceArgs a)
   a.loc_out[3 * b + 2] = a.loc[3 * b + 2] + u[2] * dt;
   const double px = u[3] * dt, py = u[4] * dt, pz = u[5] * dt;
   const double nrm = sqrt(px * px + py * py + pz * pz);
-  const double qs = cos(0.5 * nrm), f = nrm > 0.0 ? sin(0.5 * nrm) / nrm : 0.0;
+  // nrm = 0: no rotation, or |omega dt| < 1.5e-162 whose squares underflow -- f takes its limit 1/2 (with f = 0 the latter lost
+  // the whole rotation; omega dt = 0 still returns the input quaternion bit for bit)
+  const double qs = cos(0.5 * nrm), f = nrm > 0.0 ? sin(0.5 * nrm) / nrm : 0.5;
   const double qx = f * px, qy = f * py, qz = f * pz;
   const double rs = a.quat[4 * b], rx = a.quat[4 * b + 1], ry = a.quat[4 * b + 2], rz = a.quat[4 * b + 3];
   a.quat_out[4 * b] = qs * rs - (qx * rx + qy * ry + qz * rz);
@@ -266,8 +268,10 @@ __global__ __launch_bounds__(kPcT) void rigid_pc_kernel(const PcArgs a) {
   __syncthreads();
   for (int idx = t; idx < n * n; idx += kPcT) {
     const int i = idx / n, j = idx - i * n;
-    double s = A[idx];
-    for (int c = 0; c < 6; ++c) s += A12l[i * 6 + c] * MK[j * 6 + c];
+    // the lower-triangle element for both (i, j) and (j, i): A12 (M_b^-1 K)^T is symmetric only to rounding, A11 must be exactly
+    const int p = i > j ? i : j, q = i > j ? j : i;
+    double s = A[p * n + q];
+    for (int c = 0; c < 6; ++c) s += A12l[p * 6 + c] * MK[q * 6 + c];
     a.A11[b * (long)n * n + idx] = s;
   }
   if (t == 0 && bad) atomicOr(a.info, 1);
@@ -394,8 +398,9 @@ __global__ __launch_bounds__(kPcLargeT) void rigid_pc_large_kernel(const PcArgs 
     double s = 0.0;
     for (int k = (i > j ? i : j); k < n; ++k) s += A[k * n + i] * A[k * n + j];
     a.Minv[b * (long)n * n + idx] = s;
+    const int p = i > j ? i : j, q = i > j ? j : i;     // the lower-triangle element on both sides: A11 exactly symmetric
     double s11 = s;
-    for (int c = 0; c < 6; ++c) s11 += A12l[i * 6 + c] * MK[j * 6 + c];
+    for (int c = 0; c < 6; ++c) s11 += A12l[p * 6 + c] * MK[q * 6 + c];
     a.A11[b * (long)n * n + idx] = s11;
   }
   if (t == 0 && bad) atomicOr(a.info, 1);
