@@ -27,9 +27,11 @@
 //   pair<GUARDED>(a, st, self, q, take) one pair; `take` is true in the loop and lane < 32 at the peeled step
 // Padding (the lanes past n of a partial last tile) is staged as points 2e100 apart with .w = PAD_W; pair() must make
 // nothing of them.
+// The walk below stays its own loop, not sym_walk (sym_walk.h): FRAMES needs a hook at the unit advance that no other sweep uses.
 #pragma once
 #include "pair_ops.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -56,10 +58,7 @@ __device__ __forceinline__ double image(double L, double iL, double d) {
 }
 
 // the number of this wave in the walk (and of its slot in any per-wave output)
-__device__ __forceinline__ long pair_once_wave(const PairOnceArgs& a) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  return (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-}
+__device__ __forceinline__ long pair_once_wave(const PairOnceArgs& a) { return sym_wave(a.xcd); }
 
 // steps [kb, kl) of a unit, then the peeled step 32
 template <class OP, bool GUARDED>
@@ -79,7 +78,7 @@ __device__ __forceinline__ void pair_once_steps(const typename OP::Args& a, type
 template <class OP>
 __device__ __forceinline__ void pair_once_sweep(const typename OP::Args& a, typename OP::Lane& st, double4* rec) {
   const int lane = threadIdx.x & 63;
-  const long n_waves = (long)gridDim.x * kSymWaves;
+  const long n_waves = sym_n_waves();
   const long w = pair_once_wave(a);
   const long spw = a.chunk_steps > 0 ? a.chunk_steps : (a.step_end + n_waves - 1) / n_waves;
   for (long chunk = w;; chunk += n_waves) {
@@ -122,9 +121,7 @@ __device__ __forceinline__ void pair_once_sweep(const typename OP::Args& a, type
           rec[lane] = make_double4(vi_ok ? self.x : -1e100, vi_ok ? self.y : -1e100, vi_ok ? self.z : -1e100, self.w);
           if (k0 == 0) OP::diag_start(a, st, self, vi_ok);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int kb = (diag && k0 < 1) ? 1 : k0;
         const int ke = (diag && k1 > 33) ? 33 : k1;
         // step 32 of a diagonal unit is met from both of its lanes: it is peeled off the loop and taken by the lower half

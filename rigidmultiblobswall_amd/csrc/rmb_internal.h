@@ -42,6 +42,10 @@
 //   pair_table_kernels.h (a header) the tabulated radial pair law: what TableLaw of the force sweep (rmb_sym.hip) and the TABLE
 //                    instances of the energy sweep (rmb_potential.hip) share -- LDS staging, interval lookup, the two cubics;
 //                    rmb_ctx_set_pair_table and the force entry points are in rmb_entry.hip
+//   sym_walk.h (a header) the walk of a wave over its step range, written once (strided chunks, unit_seek at the chunk start,
+//                    the [k0, k1) part of a unit, row change and flush, cull skip, unit_next): sym_kernel, sym2_kernel and
+//                    sym_force_kernel are body structs under it; wave numbering (sym_wave) and wave_lds_sync
+//                    for the whole family; plain arithmetic, run on the host by tests/test_sym_walk_host.py
 //   lag_sweep_host.h (a header, included by the three units above) the checks of a batch of frames and of a lag / origin
 //                    range, pad256, and the one launch plan of the lag sweeps (plan_lag_sweep)
 #pragma once

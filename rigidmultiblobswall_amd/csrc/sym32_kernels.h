@@ -26,6 +26,7 @@
 #include "sym_force_kernels.h"
 #include "sym_kernels.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -41,6 +42,10 @@ __device__ __forceinline__ void pair_tt_sym32(const f32::PairConsts& k, float dx
   f32::tt_apply<WALL, false>(c, g, vi, vj, ui, t);
 }
 
+// The walk is sym_walk's (sym_walk.h) but still written out: on it the pair loops keep their instruction counts and the
+// kernel its registers, yet the product at 1e5 blobs measured 0.1 to 1.2 % slower than the parent's in five pairs of runs
+// out of five (profiles/r30_sym_walk.txt), cause not found.  The `if` before the seek is always true; it stays, here and in
+// the other kernels that write the loop out, so that their device code is the parent's byte for byte.
 template <bool WALL>
 __global__ __launch_bounds__(64 * kSymWaves) void sym32_tt_kernel(const SymArgs a, const f32::PairConsts kf) {
   __shared__ float rec_all[kSymWaves][9 * 64];     // planes x, y, z (float heads), their tails, vx, vy, vz of tile J
@@ -51,12 +56,9 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym32_tt_kernel(const SymArgs 
   double* accj = accj_all[wave];
 
   // the static, exactly balanced schedule of sym_kernel
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
-  for (long chunk = w;; chunk += (long)gridDim.x * kSymWaves) {
+  const long w = sym_wave(a.xcd);
+  // the walk of sym_walk.h, written out here (see the note above the kernel)
+  for (long chunk = w;; chunk += sym_n_waves()) {
   long s = a.step_begin + chunk * a.steps_per_wave;
   if (s >= a.step_end) break;
   long s_end = s + a.steps_per_wave;
@@ -108,9 +110,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym32_tt_kernel(const SymArgs 
       rec[384 + lane] = xjl; rec[448 + lane] = yjl; rec[512 + lane] = zjl;
       accj[lane] = 0; accj[64 + lane] = 0; accj[128 + lane] = 0;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const bool diag = I == J;
     // diagonal units: every ordered pair of the tile once, forward only, step 0 (the blob itself) left to finalize
@@ -135,9 +135,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym32_tt_kernel(const SymArgs 
       }
     }
     if (!diag) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const long j = 64L * J + lane;
       if (j < a.n) {
         __hip_atomic_fetch_add(&a.acc[j], accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -166,6 +164,8 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym32_tt_kernel(const SymArgs 
 // radii (RADII); separations from the head / tail split of the fp64 positions, so the exponent (2a - r)/b does not lose
 // accuracy in large domains (the reference's float kernel subtracts rounded coordinates).  Context option "precision" = 32.
 // ---------------------------------------------------------------------------------------------
+// The walk is sym_walk's (sym_walk.h) but still written out: on it the RADII instance goes from 58 to 56 VGPRs, which is
+// another allocation block.  The always-true `if` before the seek stays, so that the device code is the parent's.
 template <bool RADII>
 __global__ __launch_bounds__(64 * kSymWaves) void sym_force32_kernel(const SymForceArgs a) {
   __shared__ float4 rec_all[kSymWaves][64];       // (x, y, z) float heads of the positions, w = radius
@@ -176,14 +176,10 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force32_kernel(const SymFo
   float4* rec = rec_all[wave];
   float4* tail = tail_all[wave];
   double* accj = accj_all[wave];
-  const long n_waves = (long)gridDim.x * kSymWaves;
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  const long s_total = a.step_end - a.step_begin;
-  const long spw = a.chunk_steps > 0 ? a.chunk_steps : (s_total + n_waves - 1) / n_waves;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
+  const long n_waves = sym_n_waves();
+  const long w = sym_wave(a.xcd);
+  const long spw = sym_force_spw(a, n_waves);
+  // the walk of sym_walk.h, written out here (see the note above the kernel)
   for (long chunk = w;; chunk += n_waves) {
   long s = a.step_begin + chunk * spw;
   if (s >= a.step_end) break;
@@ -242,9 +238,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force32_kernel(const SymFo
       tail[lane] = ql;
       accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const bool diag = (I == J);
     for (int k = (diag && k0 < 1) ? 1 : k0; k < k1; ++k) {
       const int jj = (lane + k) & 63;
@@ -266,9 +260,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force32_kernel(const SymFo
       }
     }
     if (!diag) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const long j = 64L * J + lane;
       if (j < a.n) {
         __hip_atomic_fetch_add(&a.acc[j], -accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -9,6 +9,7 @@
 #include "pair_ops.h"
 #include "pair_table_kernels.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -98,55 +99,45 @@ __device__ __forceinline__ void pair_force(const SymForceArgs& a, double two_a, 
   fx = f0 * dx; fy = f0 * dy; fz = f0 * dz;
 }
 
+// steps per chunk of the force sweeps: the planned chunk, or one contiguous range per wave
+__device__ __forceinline__ long sym_force_spw(const SymForceArgs& a, long n_waves) {
+  return a.chunk_steps > 0 ? a.chunk_steps : (a.step_end - a.step_begin + n_waves - 1) / n_waves;
+}
+
 template <bool PERIODIC, bool RADII = false, class LAW = BlobContactLaw>
 __global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForceArgs a) {
   __shared__ double4 rec_all[kSymWaves][64];
   __shared__ double accj_all[kSymWaves][3 * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  double4* rec = rec_all[wave];
-  double* accj = accj_all[wave];
-  if constexpr (LAW::STAGED) stage_pair_table(a.tab);      // once per workgroup, before any wave starts its walk
-  const long n_waves = (long)gridDim.x * kSymWaves;
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  const long s_total = a.step_end - a.step_begin;
-  const long spw = a.chunk_steps > 0 ? a.chunk_steps : (s_total + n_waves - 1) / n_waves;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
-  for (long chunk = w;; chunk += n_waves) {
-  long s = a.step_begin + chunk * spw;
-  if (s >= a.step_end) break;
-  long s_end = s + spw;
-  if (s_end > a.step_end) s_end = a.step_end;
-  int I = 0, J = 0;
-  if (s < s_end) unit_seek(a.order, s >> 6, a.n_tiles, I, J);
-  int I_cur = -1;
-  long i = 0;
-  bool vi_ok = false;
-  double xi = 0, yi = 0, zi = 0, ri = 0;
-  double ax = 0, ay = 0, az = 0;
-  while (s < s_end) {
-    const int k0 = (int)(s & 63);
-    const long left = s_end - s;
-    const int k1 = (left < 64 - k0) ? (int)(k0 + left) : 64;
-    s += k1 - k0;
-    if (a.bounds != nullptr && I != J &&
-        tile_gap2(a.bounds, I, J, PERIODIC ? a.Lx : 0.0, PERIODIC ? a.Ly : 0.0, PERIODIC ? a.Lz : 0.0) > a.cull2) {
-      // every pair of this unit is beyond the range of the exponential: contributes exactly zero
-      if (k1 == 64) {
-        unit_next(a.order, a.n_tiles, I, J);
-      }
-      continue;
+
+  struct Body {
+    const SymForceArgs& a;
+    const int lane;
+    double4* const rec;
+    double* const accj;
+    long i;
+    bool vi_ok;
+    double xi, yi, zi, ri;
+    double ax, ay, az;
+
+    __device__ __forceinline__ Body(const SymForceArgs& a, int lane, double4* rec, double* accj) : a(a), lane(lane), rec(rec), accj(accj) {}
+    __device__ __forceinline__ void begin() {
+      i = 0;
+      vi_ok = false;
+      xi = 0; yi = 0; zi = 0; ri = 0;
+      ax = 0; ay = 0; az = 0;
     }
-    if (I != I_cur) {
-      if (I_cur >= 0 && vi_ok) {
-        __hip_atomic_fetch_add(&a.acc[i], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      I_cur = I;
+    // every pair of the unit is beyond the range of the exponential: contributes exactly zero
+    __device__ __forceinline__ bool culled(int I, int J) const {
+      return a.bounds != nullptr && I != J &&
+             tile_gap2(a.bounds, I, J, PERIODIC ? a.Lx : 0.0, PERIODIC ? a.Ly : 0.0, PERIODIC ? a.Lz : 0.0) > a.cull2;
+    }
+    __device__ __forceinline__ void flush_row(long) {
+      if (!vi_ok) return;
+      __hip_atomic_fetch_add(&a.acc[i], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void load_row(int I) {
       i = 64L * I + lane;
       vi_ok = i < a.n;
       xi = 1e100; yi = 1e100; zi = 1e100;
@@ -154,54 +145,49 @@ __global__ __launch_bounds__(64 * kSymWaves) void sym_force_kernel(const SymForc
       if constexpr (RADII) ri = vi_ok ? a.radii[i] : 0.0;
       ax = 0.0; ay = 0.0; az = 0.0;
     }
-    {
-      const long j = 64L * J + lane;
-      double4 p = make_double4(-1e100, -1e100, -1e100, 0.0);
-      if (j < a.n) p = a.pos[j];
-      if constexpr (RADII) p.w = (j < a.n) ? a.radii[j] : 0.0;   // w is free here: forces use unclamped positions (b = 1)
-      rec[lane] = p;
-      accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool diag = (I == J);
-    for (int k = (diag && k0 < 1) ? 1 : k0; k < k1; ++k) {
-      const int jj = (lane + k) & 63;
-      const double4 q = rec[jj];
-      double fx, fy, fz;
-      pair_force<PERIODIC, LAW>(a, RADII ? ri + q.w : a.two_a, q.x - xi, q.y - yi, q.z - zi, fx, fy, fz);
-      ax += fx; ay += fy; az += fz;
-      if (!diag) {   // wave-uniform
-        // the LDS slab collects +f (ds_add_f64 has no negate modifier: -f would cost a v_xor + v_mov per component
-        // and step); the sign of the reaction goes into the flush below
-        __hip_atomic_fetch_add(&accj[jj], fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(&accj[64 + jj], fy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(&accj[128 + jj], fz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __device__ __forceinline__ void unit(int I, int J, int k0, int k1, long) {
+      {
+        const long j = 64L * J + lane;
+        double4 p = make_double4(-1e100, -1e100, -1e100, 0.0);
+        if (j < a.n) p = a.pos[j];
+        if constexpr (RADII) p.w = (j < a.n) ? a.radii[j] : 0.0;   // w is free here: forces use unclamped positions (b = 1)
+        rec[lane] = p;
+        accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
       }
-    }
-    if (!diag) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const long j = 64L * J + lane;
-      if (j < a.n) {
-        __hip_atomic_fetch_add(&a.acc[j], -accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[a.n_pad + j], -accj[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + j], -accj[128 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      wave_lds_sync();
+      const bool diag = (I == J);
+      for (int k = (diag && k0 < 1) ? 1 : k0; k < k1; ++k) {
+        const int jj = (lane + k) & 63;
+        const double4 q = rec[jj];
+        double fx, fy, fz;
+        pair_force<PERIODIC, LAW>(a, RADII ? ri + q.w : a.two_a, q.x - xi, q.y - yi, q.z - zi, fx, fy, fz);
+        ax += fx; ay += fy; az += fz;
+        if (!diag) {   // wave-uniform
+          // the LDS slab collects +f (ds_add_f64 has no negate modifier: -f would cost a v_xor + v_mov per component
+          // and step); the sign of the reaction goes into the flush below
+          __hip_atomic_fetch_add(&accj[jj], fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          __hip_atomic_fetch_add(&accj[64 + jj], fy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          __hip_atomic_fetch_add(&accj[128 + jj], fz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
       }
+      if (!diag) {
+        wave_lds_sync();
+        const long j = 64L * J + lane;
+        if (j < a.n) {
+          __hip_atomic_fetch_add(&a.acc[j], -accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(&a.acc[a.n_pad + j], -accj[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + j], -accj[128 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();   // accj / rec are rewritten by the next unit
     }
-    __builtin_amdgcn_wave_barrier();
-    if (k1 == 64) {
-      unit_next(a.order, a.n_tiles, I, J);
-    }
-  }
-  if (I_cur >= 0 && vi_ok) {
-    __hip_atomic_fetch_add(&a.acc[i], ax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], az, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  }   // chunks
+  };
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  Body body(a, threadIdx.x & 63, rec_all[wave], accj_all[wave]);
+  if constexpr (LAW::STAGED) stage_pair_table(a.tab);      // once per workgroup, before any wave starts its walk
+  const long n_waves = sym_n_waves();
+  sym_walk(SymWalk{a.order, a.n_tiles, a.step_begin, a.step_end, sym_force_spw(a, n_waves), n_waves, sym_wave(a.xcd)}, body);
 }
 
 static __global__ __launch_bounds__(256) void sym_force_finalize_kernel(const SymForceArgs a) {

@@ -29,6 +29,7 @@
 #pragma once
 #include "pair_blocks.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -136,49 +137,33 @@ template <int KIND, bool WALL, bool PERIODIC>
 __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(kSymWavesPerEu, kSymWavesPerEu))) void sym_kernel(const SymArgs a) {
   __shared__ double2 rec_all[kSymWaves][64 * 3];
   __shared__ double accj_all[kSymWaves][3 * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  double2* rec = rec_all[wave];
-  double* accj = accj_all[wave];
-  const char* rec_bytes = reinterpret_cast<const char*>(rec);
-  constexpr bool Z2 = kSymZi2<KIND, WALL>;      // wall tt: zi holds the doubled height 2 z_i (see pair_sym)
+  static constexpr bool Z2 = kSymZi2<KIND, WALL>;      // wall tt: zi holds the doubled height 2 z_i (see pair_sym)
 
-  // Static, exactly balanced schedule: the n_units * 64 rotation steps are cut into gridDim.x * 4 equal
-  // contiguous ranges, one per wave; a range may begin and end inside a unit.
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  const long long t_start = a.wave_clock ? wall_clock64() : 0;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
-  for (long chunk = w;; chunk += (long)gridDim.x * kSymWaves) {
-  long s = a.step_begin + chunk * a.steps_per_wave;
-  if (s >= a.step_end) break;
-  long s_end = s + a.steps_per_wave;
-  if (s_end > a.step_end) s_end = a.step_end;
-  // decode the first unit once (row-major upper triangle); later units follow by increment
-  int I = 0, J = 0;
-  if (s < s_end) unit_seek(a.order, s >> 6, a.n_tiles, I, J);
+  struct Body {
+    const SymArgs& a;
+    const int lane;
+    double2* const rec;
+    double* const accj;
+    long i;
+    bool vi_ok;
+    double xi, yi, zi, vix, viy, viz;
+    Vec3 ui;
 
-  int I_cur = -1;
-  long i = 0;
-  bool vi_ok = false;
-  double xi = 0, yi = 0, zi = sym_height<Z2>(1.0), vix = 0, viy = 0, viz = 0;
-  Vec3 ui = {0.0, 0.0, 0.0};
-
-  while (s < s_end) {
-    const int k0 = (int)(s & 63);
-    const long left = s_end - s;
-    const int k1 = (left < 64 - k0) ? (int)(k0 + left) : 64;
-    s += k1 - k0;
-
-    if (I != I_cur) {
-      if (I_cur >= 0 && vi_ok) {   // flush the previous row's accumulator
-        __hip_atomic_fetch_add(&a.acc[i], ui.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ui.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], ui.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      I_cur = I;
+    __device__ __forceinline__ Body(const SymArgs& a, int lane, double2* rec, double* accj) : a(a), lane(lane), rec(rec), accj(accj) {}
+    __device__ __forceinline__ void begin() {
+      i = 0;
+      vi_ok = false;
+      xi = 0; yi = 0; zi = sym_height<Z2>(1.0); vix = 0; viy = 0; viz = 0;
+      ui.x = 0.0; ui.y = 0.0; ui.z = 0.0;
+    }
+    __device__ __forceinline__ bool culled(int, int) const { return false; }
+    __device__ __forceinline__ void flush_row(long) {
+      if (!vi_ok) return;
+      __hip_atomic_fetch_add(&a.acc[i], ui.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ui.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], ui.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void load_row(int I) {
       i = 64L * I + lane;
       vi_ok = i < a.n;
       xi = 1e100; yi = 1e100; zi = sym_height<Z2>(1.0); vix = 0; viy = 0; viz = 0;
@@ -189,98 +174,96 @@ __global__ __launch_bounds__(64 * kSymWaves) __attribute__((amdgpu_waves_per_eu(
       }
       ui.x = 0.0; ui.y = 0.0; ui.z = 0.0;
     }
-    // tile J -> this wave's LDS slab (record l = blob 64 J + l), zero its accumulators
-    {
-      const long j = 64L * J + lane;
-      double xj = -1e100, yj = -1e100, zj = 1.0, vjx = 0, vjy = 0, vjz = 0;
-      if (j < a.n) {
-        const double4 p = a.pos[j];
-        xj = p.x; yj = p.y; zj = p.z;
-        vjx = a.vec[3 * j] * p.w; vjy = a.vec[3 * j + 1] * p.w; vjz = a.vec[3 * j + 2] * p.w;
+    __device__ __forceinline__ void unit(int I, int J, int k0, int k1, long) {
+      const char* rec_bytes = reinterpret_cast<const char*>(rec);
+      // tile J -> this wave's LDS slab (record l = blob 64 J + l), zero its accumulators
+      {
+        const long j = 64L * J + lane;
+        double xj = -1e100, yj = -1e100, zj = 1.0, vjx = 0, vjy = 0, vjz = 0;
+        if (j < a.n) {
+          const double4 p = a.pos[j];
+          xj = p.x; yj = p.y; zj = p.z;
+          vjx = a.vec[3 * j] * p.w; vjy = a.vec[3 * j + 1] * p.w; vjz = a.vec[3 * j + 2] * p.w;
+        }
+        rec[lane * 3 + 0] = make_double2(xj, yj);
+        rec[lane * 3 + 1] = make_double2(zj, vjx);
+        rec[lane * 3 + 2] = make_double2(vjy, vjz);
+        accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
       }
-      rec[lane * 3 + 0] = make_double2(xj, yj);
-      rec[lane * 3 + 1] = make_double2(zj, vjx);
-      rec[lane * 3 + 2] = make_double2(vjy, vjz);
-      accj[lane] = 0.0; accj[64 + lane] = 0.0; accj[128 + lane] = 0.0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
 
-    // Pseudo-periodic images (mobility_numba.py:170-197): nearest image once, then the 3^d neighbour boxes.
-    // M_ji(box b) = M_ij(box -b)^T and the boxes are summed symmetrically, so both directions of every image
-    // are still evaluated together.
-    const int px = PERIODIC && a.Lx > 0, py = PERIODIC && a.Ly > 0, pz = PERIODIC && a.Lz > 0;
-    if (I != J) {
-      for (int k = (a.skip_pairs & 1) ? k1 : k0; k < k1; ++k) {
-        const int jj = (lane + k) & 63;
-        const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
-        const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
-        double tx, ty, tz;
-        if constexpr (!PERIODIC) {
-          pair_sym<KIND, WALL, false, Z2>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
-        } else {
-          if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
-          if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
-          if (pz) dz = wrap_nearest_pad_safe(dz, a.Lz, a.iLz);
-          tx = 0.0; ty = 0.0; tz = 0.0;
-          for (int bx = -px; bx <= px; ++bx)
-            for (int by = -py; by <= py; ++by)
-              for (int bz = -pz; bz <= pz; ++bz) {
-                pair_sym<KIND, WALL, true, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
-                                           q2.y, ui, tx, ty, tz);      // accumulates (fused multiply-adds)
-              }
+      // Pseudo-periodic images (mobility_numba.py:170-197): nearest image once, then the 3^d neighbour boxes.
+      // M_ji(box b) = M_ij(box -b)^T and the boxes are summed symmetrically, so both directions of every image
+      // are still evaluated together.
+      const int px = PERIODIC && a.Lx > 0, py = PERIODIC && a.Ly > 0, pz = PERIODIC && a.Lz > 0;
+      if (I != J) {
+        for (int k = (a.skip_pairs & 1) ? k1 : k0; k < k1; ++k) {
+          const int jj = (lane + k) & 63;
+          const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
+          const double2 q0 = r[0], q1 = r[1], q2 = r[2];
+          double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
+          double tx, ty, tz;
+          if constexpr (!PERIODIC) {
+            pair_sym<KIND, WALL, false, Z2>(a.k, dx, dy, dz, zi, q1.x, vix, viy, viz, q1.y, q2.x, q2.y, ui, tx, ty, tz);
+          } else {
+            if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
+            if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
+            if (pz) dz = wrap_nearest_pad_safe(dz, a.Lz, a.iLz);
+            tx = 0.0; ty = 0.0; tz = 0.0;
+            for (int bx = -px; bx <= px; ++bx)
+              for (int by = -py; by <= py; ++by)
+                for (int bz = -pz; bz <= pz; ++bz) {
+                  pair_sym<KIND, WALL, true, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, vix, viy, viz, q1.y, q2.x,
+                                             q2.y, ui, tx, ty, tz);      // accumulates (fused multiply-adds)
+                }
+          }
+          __hip_atomic_fetch_add(&accj[jj], tx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          __hip_atomic_fetch_add(&accj[64 + jj], ty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          __hip_atomic_fetch_add(&accj[128 + jj], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
-        __hip_atomic_fetch_add(&accj[jj], tx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(&accj[64 + jj], ty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_add(&accj[128 + jj], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const long j = 64L * J + lane;
-      if (j < a.n && !(a.skip_pairs & 2)) {
-        __hip_atomic_fetch_add(&a.acc[j], accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[a.n_pad + j], accj[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + j], accj[128 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    } else {
-      // diagonal unit: every ordered pair of the tile once, forward only.  Step 0 is the blob itself: its
-      // central-box term is the self term (finalize); its periodic images use the pair formula.
-      for (int k = (a.skip_pairs & 1) ? k1 : ((PERIODIC || k0 > 1) ? k0 : 1); k < k1; ++k) {
-        const int jj = (lane + k) & 63;
-        const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
-        const double2 q0 = r[0], q1 = r[1], q2 = r[2];
-        double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
-        if constexpr (!PERIODIC) {
-          pair_apply<KIND, WALL, Z2>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
-        } else {
-          if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
-          if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
-          if (pz) dz = wrap_nearest_pad_safe(dz, a.Lz, a.iLz);
-          for (int bx = -px; bx <= px; ++bx)
-            for (int by = -py; by <= py; ++by)
-              for (int bz = -pz; bz <= pz; ++bz) {
-                if (k == 0 && bx == 0 && by == 0 && bz == 0) continue;
-                pair_apply<KIND, WALL, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
-                                       0.0, ui);
-              }
+        wave_lds_sync();
+        const long j = 64L * J + lane;
+        if (j < a.n && !(a.skip_pairs & 2)) {
+          __hip_atomic_fetch_add(&a.acc[j], accj[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(&a.acc[a.n_pad + j], accj[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + j], accj[128 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else {
+        // diagonal unit: every ordered pair of the tile once, forward only.  Step 0 is the blob itself: its
+        // central-box term is the self term (finalize); its periodic images use the pair formula.
+        for (int k = (a.skip_pairs & 1) ? k1 : ((PERIODIC || k0 > 1) ? k0 : 1); k < k1; ++k) {
+          const int jj = (lane + k) & 63;
+          const double2* r = reinterpret_cast<const double2*>(rec_bytes + jj * kSymRecBytes);
+          const double2 q0 = r[0], q1 = r[1], q2 = r[2];
+          double dx = xi - q0.x, dy = yi - q0.y, dz = sym_dz<Z2>(zi, q1.x);
+          if constexpr (!PERIODIC) {
+            pair_apply<KIND, WALL, Z2>(a.k, dx, dy, dz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0, 0.0, ui);
+          } else {
+            if (px) dx = wrap_nearest_pad_safe(dx, a.Lx, a.iLx);
+            if (py) dy = wrap_nearest_pad_safe(dy, a.Ly, a.iLy);
+            if (pz) dz = wrap_nearest_pad_safe(dz, a.Lz, a.iLz);
+            for (int bx = -px; bx <= px; ++bx)
+              for (int by = -py; by <= py; ++by)
+                for (int bz = -pz; bz <= pz; ++bz) {
+                  if (k == 0 && bx == 0 && by == 0 && bz == 0) continue;
+                  pair_apply<KIND, WALL, Z2>(a.k, dx + bx * a.Lx, dy + by * a.Ly, dz + bz * a.Lz, zi, q1.x, q1.y, q2.x, q2.y, 0.0, 0.0,
+                                         0.0, ui);
+                }
+          }
         }
       }
+      __builtin_amdgcn_wave_barrier();   // accj / rec are rewritten by the next unit
     }
-    __builtin_amdgcn_wave_barrier();   // accj / rec are rewritten by the next unit
-    if (k1 == 64) {                    // next unit in row-major order
-      unit_next(a.order, a.n_tiles, I, J);
-    }
-  }
-  if (I_cur >= 0 && vi_ok) {
-    __hip_atomic_fetch_add(&a.acc[i], ui.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&a.acc[a.n_pad + i], ui.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&a.acc[2 * a.n_pad + i], ui.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  }   // chunks
-  if (a.wave_clock && lane == 0) {   // stamps go to a buffer nothing else reads
+  };
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  Body body(a, threadIdx.x & 63, rec_all[wave], accj_all[wave]);
+  // Static, exactly balanced schedule: the n_units * 64 rotation steps are cut into equal contiguous ranges, one per
+  // chunk of a wave; a range may begin and end inside a unit (sym_walk.h).
+  const long w = sym_wave(a.xcd);
+  const long long t_start = a.wave_clock ? wall_clock64() : 0;
+  sym_walk(SymWalk{a.order, a.n_tiles, a.step_begin, a.step_end, a.steps_per_wave, sym_n_waves(), w}, body);
+  if (a.wave_clock && body.lane == 0) {   // stamps go to a buffer nothing else reads
     // placement: HW_ID (reg 4: simd [5:4], cu [11:8], sh [12], se [15:13]) and XCC_ID (reg 20) in the top 24 bits
     const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | ((16 - 1) << 11));
     const unsigned xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11));

@@ -15,6 +15,7 @@
 #include "symx_kernels.h"
 #include "sym32_kernels.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -222,6 +223,10 @@ template <class OP> struct SymX32Lds {
   static constexpr size_t bytes = (sizeof(float) * planes + sizeof(double) * 3 * OP::NOUT) * 64 * kSymWaves;
 };
 
+// The walk is sym_walk's (sym_walk.h) but still written out, for the reason given at symx_kernel: with the lane arrays in
+// a body struct the pair loops of the OpKindK32 instances gain 5 to 12 register copies and OpKindK32<3, 4> wall goes
+// from 91 to 97 VGPRs, one allocation block up.  The always-true `if` before the seek stays: dropping it alone moves
+// OpKindK32<3, 2> wall from 73 to 72 VGPRs, another allocation block.
 template <class OP, bool WALL>
 __global__ __launch_bounds__(64 * kSymWaves) void symx32_kernel(const SymXArgs a, const f32::PairConsts kf) {
   constexpr int NI = OP::NIN, NO = OP::NOUT, NX = SymXExtra<OP>::value, NV = 3 * NI + NX, NP = 6 + NV;
@@ -232,12 +237,9 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx32_kernel(const SymXArgs a
   float* rec = rec_all[wave];
   double* accj = accj_all[wave];
 
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
-  for (long chunk = w;; chunk += (long)gridDim.x * kSymWaves) {
+  const long w = sym_wave(a.xcd);
+  // the walk of sym_walk.h, written out here (see the note above the kernel)
+  for (long chunk = w;; chunk += sym_n_waves()) {
   long s = a.step_begin + chunk * a.steps_per_wave;
   if (s >= a.step_end) break;
   long s_end = s + a.steps_per_wave;
@@ -312,9 +314,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx32_kernel(const SymXArgs a
 #pragma unroll
       for (int c = 0; c < 3 * NO; ++c) accj[c * 64 + lane] = 0.0;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const bool diag = I == J;
     // diagonal units: every ordered pair of the tile once, forward only; step 0 (the blob itself) is the self term
@@ -336,9 +336,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx32_kernel(const SymXArgs a
       }
     }
     if (!diag) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const long j = 64L * J + lane;
       if (j < a.n) {
 #pragma unroll

@@ -27,6 +27,7 @@
 #pragma once
 #include "sym_kernels.h"
 #include "sym_schedule.h"
+#include "sym_walk.h"
 
 namespace rmb {
 
@@ -359,6 +360,11 @@ template <class OP> struct SymXExtra<OP, decltype((void)OP::NEXTRA)> { static co
 // (Measured and dropped: storing every record / accumulator slot twice so that the rotation index lane + k needs no
 //  `& 63` wrap removes 2 of the 4 integer instructions per step -- 106 -> 104 -- and changes nothing in time,
 //  0.1853 vs 0.1849 ms at 1e4 blobs, 17.17 vs 17.27 ms at 1e5: the integer work already hides under fp64 issue.)
+// The walk is sym_walk's (sym_walk.h) but still written out: as a body struct the lane arrays vi / ui live for the whole
+// kernel instead of one chunk, and the register allocation then moves -- seven instances change their VGPR allocation
+// block (OpColumnF 82 -> 80, OpKindK<1|2, 2> 89 -> 88, ...), which changes residency and with it the launch plan.
+// flush_row(unit_before) and the unit index of sym_walk's hooks are what the DET slots below would take; until this kernel
+// moves no body reads them.  The always-true `if` before the seek stays: without it the device code is not the parent's.
 template <class OP, bool WALL, bool PERIODIC, bool DET = false>
 __global__ __launch_bounds__(64 * kSymWaves) void symx_kernel(const SymXArgs a) {
   constexpr int NI = OP::NIN, NO = OP::NOUT, NX = SymXExtra<OP>::value;
@@ -372,12 +378,9 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx_kernel(const SymXArgs a) 
   double* accj = accj_all[wave];
   const char* rec_bytes = reinterpret_cast<const char*>(rec);
 
-  const long w = (a.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (long)blockIdx.x) * kSymWaves + wave;
-  // strided chunks: wave / workgroup `id` takes the step ranges id, id + n, id + 2 n, ... of `spw` steps each (one range when
-  // the launch is planned that way: n spw >= the steps of the launch).  Waves that run at the same time then work on
-  // NEIGHBOURING ranges whatever the size of the problem -- with the blocked unit order and the XCD-aware numbering
-  // that keeps a launch's tile loads in one L2 (profiles/r4_unit_order.txt).
-  for (long chunk = w;; chunk += (long)gridDim.x * kSymWaves) {
+  const long w = sym_wave(a.xcd);
+  // the walk of sym_walk.h, written out here (see the note above the kernel)
+  for (long chunk = w;; chunk += sym_n_waves()) {
   long s = a.step_begin + chunk * a.steps_per_wave;
   if (s >= a.step_end) break;
   long s_end = s + a.steps_per_wave;
@@ -458,9 +461,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx_kernel(const SymXArgs a) 
 #pragma unroll
       for (int c = 0; c < 3 * NO; ++c) accj[c * 64 + lane] = 0.0;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const int px = PERIODIC && a.Lx > 0, py = PERIODIC && a.Ly > 0, pz = PERIODIC && a.Lz > 0;
     const bool diag = I == J;
@@ -498,9 +499,7 @@ __global__ __launch_bounds__(64 * kSymWaves) void symx_kernel(const SymXArgs a) 
       }
     }
     if (!diag) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const long j = 64L * J + lane;
       if constexpr (DET) {
         double* p = a.part_J + (unit - a.unit_begin) * (3 * NO * 64) + lane;
