@@ -588,6 +588,36 @@ int rmb_bond_order_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_
                                  const int* orders, int n_orders, long source_chunk, double* out_dev);
 int rmb_pair_field_frames_device(rmb_ctx* ctx, const double* frames_dev, const int* field_dev, long n_frames, long n, const double* L,
                                  int plane, double r_max, long n_bins, unsigned long long* counts_dev, long long* sums_dev);
+/* Cluster analysis (cluster_kernels.h; clusters.py): the connected components of the bond graph of a point configuration.
+ * Points i and j of one frame are bonded when d_ij < r_cut, strictly (compared as d^2 < r_cut^2 in fp64): the separation in the
+ * minimal image of every direction with a positive period (rmb_pair_histogram's formula, any number of periods away); plane = 0
+ * (xyz): the three-dimensional distance; plane = 1 (xy): the in-plane distance, z and L_z ignored.  Coincident points, and
+ * stacked points under xy, have d = 0 and ARE bonded (unlike the neighbours of rmb_bond_order_frames_device).  A cluster is a
+ * connected component; the label of a point is the smallest caller index in its cluster.  select = one byte per point on the
+ * device (non-zero: selected) or NULL (all): only bonds between two selected points exist; an unselected point gets label -1
+ * and belongs to no cluster.
+ *   labels[f, i]  int32: the label of point i of frame f (an index within the frame), -1 when unselected;
+ *   sizes[f, l]   int32: the number of points of the cluster labelled l, 0 where l is nobody's label.
+ * Both are (n_frames, n) (resident entry: n) on the device and OVERWRITTEN.  Three launches: parent = identity; the pair-once
+ * sweep, whose pair term is a lock-free union-find in global memory (the larger root is hooked under the smaller with an
+ * integer compare-and-swap; no lock, no spin-wait, no floating-point atomic); a finishing launch of one thread per point.  A
+ * root is always the minimum of its set, so labels and sizes are the same bits for every launch plan, point order, culling
+ * choice and cut of the trajectory.  The parent array lives in a workspace of the context.
+ *   rmb_cluster_labels_frames_device  n_frames frames of n points, frames_dev = (n_frames, n, 3) packed doubles, L = 3 periods on
+ *                                     the host (<= 0: open), one sweep over (frame, tile pair); n_frames * n <= 2^31 - 1 per
+ *                                     call.  Nothing of the resident configuration is read or written.
+ *   rmb_cluster_labels_device         the resident raw positions (rmb_set_positions with wall = 0; wall = 1 or a target
+ *                                     sub-range: RMB_ERR_STATE), Morton-sorted from 2048 points on ("force_sort"), tile pairs
+ *                                     further apart than r_cut skipped ("force_cull"; under plane xy the gap between two tiles
+ *                                     is taken without its z term) -- which drops no bond.
+ * Always fp64, single device, asynchronous on the context's stream.
+ * RMB_ERR_ARG, before the context or the device is touched: a null frames / L / labels / sizes pointer (one whose array is
+ * empty may be null), negative sizes, r_cut not positive and finite, plane not 0 or 1, n_frames * n above 2^31 - 1.
+ * n_frames = 0 and n = 0 touch nothing; n = 1 gives label 0 and size 1. */
+int rmb_cluster_labels_frames_device(rmb_ctx* ctx, const double* frames_dev, const unsigned char* select_dev_or_null, long n_frames, long n,
+                                     const double* L, double r_cut, int plane, int* labels_dev, int* sizes_dev);
+int rmb_cluster_labels_device(rmb_ctx* ctx, const unsigned char* select_dev_or_null, double r_cut, int plane, int* labels_dev,
+                              int* sizes_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

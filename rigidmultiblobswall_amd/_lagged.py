@@ -28,31 +28,12 @@ def lengths(periodic_length):
   return L.copy()
 
 
-class LagAccumulator(object):
-  """Streaming base of an analysis over n_lags lags (lag l = l frames = l dt) of frames (k, n, width).  add_frames(frames)
-  takes a numpy array or a CUDA float64 tensor in any number of pieces; per frame the tensors of _records() are kept
-  while the frame is an origin whose lags are not complete (at most n_lags - 1 frames: self._tail, a tuple of tensors, or
-  None), and _call(records, "window") is handed every buffer that completes at least one origin.  finish() ends the
-  trajectory: with origins="all" the frames still held are origins of the lags that exist for them.
-
-  A subclass sets `width`, `entry` (the context method it cannot do without), `what` and `row` (the words of its refusals),
-  validates its own arguments after LagAccumulator.__init__ and before _open() (which may create a context), and supplies
-  _per(), _records(piece) and _call(records, origins)."""
-  width = None      # numbers per row of a frame
+class ContextHolder(object):
+  """What the streaming analyses share whether or not they have lags: the single-GPU context they run on.  A subclass sets
+  `entry` (the context method it cannot do without) and `what` (the words of the refusal)."""
   entry = None
   what = None       # "<the analysis> run(s)": ... on a single-GPU MobilityContext
-  row = None        # (name of n, "%d <rows> x <width> <numbers>")
-
-  def __init__(self, n, n_lags, dt, origins):
-    self.n, self.n_lags, self.dt = int(n), int(n_lags), float(dt)
-    if self.n < 0:
-      raise ValueError("%s must not be negative" % self.row[0])
-    counts_per_lag(0, 1, self.n_lags, origins)      # refuses what the kernel entries would
-    self.origins = origins
-    self.n_frames = 0
-    self.ctx, self._own_ctx = None, False
-    self._finished = False
-    self._tail = None
+  ctx, _own_ctx = None, False
 
   def _open(self, device, ctx):
     """ctx: a single-GPU MobilityContext (its resident configuration is left alone); None makes one on `device`, closed by
@@ -74,6 +55,31 @@ class LagAccumulator(object):
     if self._own_ctx and self.ctx is not None:
       self.ctx.close()
     self.ctx = None
+
+
+class LagAccumulator(ContextHolder):
+  """Streaming base of an analysis over n_lags lags (lag l = l frames = l dt) of frames (k, n, width).  add_frames(frames)
+  takes a numpy array or a CUDA float64 tensor in any number of pieces; per frame the tensors of _records() are kept
+  while the frame is an origin whose lags are not complete (at most n_lags - 1 frames: self._tail, a tuple of tensors, or
+  None), and _call(records, "window") is handed every buffer that completes at least one origin.  finish() ends the
+  trajectory: with origins="all" the frames still held are origins of the lags that exist for them.
+
+  A subclass sets `width`, `entry` (the context method it cannot do without), `what` and `row` (the words of its refusals),
+  validates its own arguments after LagAccumulator.__init__ and before _open() (which may create a context), and supplies
+  _per(), _records(piece) and _call(records, origins)."""
+  width = None      # numbers per row of a frame
+  row = None        # (name of n, "%d <rows> x <width> <numbers>")
+
+  def __init__(self, n, n_lags, dt, origins):
+    self.n, self.n_lags, self.dt = int(n), int(n_lags), float(dt)
+    if self.n < 0:
+      raise ValueError("%s must not be negative" % self.row[0])
+    counts_per_lag(0, 1, self.n_lags, origins)      # refuses what the kernel entries would
+    self.origins = origins
+    self.n_frames = 0
+    self.ctx, self._own_ctx = None, False
+    self._finished = False
+    self._tail = None
 
   def _per(self):
     """frames per upload piece"""

@@ -826,6 +826,63 @@ class MobilityContext(object):
     return counts, sums
 
   @staticmethod
+  def _cluster_args(n_frames, n, plane, select, labels, sizes, device, shape, named):
+    """Checks shared by the two cluster entries -> (plane index, select as uint8 or None, labels, sizes)."""
+    import torch
+    if plane not in VAN_HOVE_PLANES:
+      raise ValueError("plane must be one of %s, got %r" % (sorted(VAN_HOVE_PLANES), plane))
+    if n_frames * n > 2 ** 31 - 1:
+      raise ValueError("n_frames * n must not exceed 2^31 - 1 per call, got %d" % (n_frames * n))
+    if select is not None:
+      if not (isinstance(select, torch.Tensor) and select.is_cuda and select.dtype in (torch.bool, torch.uint8) and select.is_contiguous() and
+              tuple(select.shape) == tuple(shape)):
+        raise ValueError("select must be a contiguous CUDA bool or uint8 tensor of shape %s" % named)
+      if select.dtype == torch.bool:
+        select = select.view(torch.uint8)      # one byte per point, 0 or 1: no copy
+    labels = _cuda_out(labels, shape, named, "int32", device, what="labels", zero=False)
+    sizes = _cuda_out(sizes, shape, named, "int32", device, what="sizes", zero=False)
+    return VAN_HOVE_PLANES[plane], select, labels, sizes
+
+  def cluster_labels_frames_device(self, frames, periodic_length, r_cut, plane="xyz", select=None, labels=None, sizes=None):
+    """Connected components of the bond graph of every frame of `frames` -- a contiguous CUDA float64 tensor (n_frames, n, 3), or
+    (n, 3) for one frame, possibly unwrapped (rmb_cluster_labels_frames_device).  Points i and j of a frame are bonded when
+    d_ij < r_cut, strictly, in the minimal image of every direction with a positive period (periodic_length: three periods, <= 0:
+    open); plane="xyz": the 3-D distance, "xy": the in-plane one (z and L_z ignored).  Coincident, and under "xy" stacked, points
+    are bonded.  select: a CUDA bool or uint8 tensor (n_frames, n) ((n,) for one frame), non-zero = selected; only bonds between
+    two selected points exist.  Returns (labels, sizes), CUDA int32 tensors of that shape, OVERWRITTEN when given: labels[f, i] =
+    the smallest index of the cluster of point i (-1: unselected), sizes[f, l] = the size of the cluster labelled l (0 where l is
+    nobody's label).  Integers that do not depend on the launch plan, the point order or the cut of the trajectory; n_frames * n
+    <= 2^31 - 1 per call (clusters.Clusters cuts its batches).  Asynchronous on torch's stream; the resident configuration is
+    neither read nor changed."""
+    if not _is_torch_cuda(frames) or not frames.is_contiguous() or frames.dim() not in (2, 3) or frames.shape[-1] != 3:
+      raise ValueError("frames must be a contiguous CUDA float64 tensor of shape (n_frames, n, 3) or (n, 3)")
+    shape = tuple(int(s) for s in frames.shape[:-1])
+    n_frames, n = (1, shape[0]) if frames.dim() == 2 else shape
+    L = _as_f64(periodic_length, 3)
+    pl, select, labels, sizes = self._cluster_args(n_frames, n, plane, select, labels, sizes, frames.device, shape,
+                                                   "(n_frames, n)" if frames.dim() == 3 else "(n,)")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_cluster_labels_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None,
+                                                          ctypes.c_void_p(select.data_ptr()) if select is not None and select.numel() else None,
+                                                          n_frames, n, _ptr(L), float(r_cut), pl,
+                                                          ctypes.c_void_p(labels.data_ptr()) if labels.numel() else None,
+                                                          ctypes.c_void_p(sizes.data_ptr()) if sizes.numel() else None))
+    return labels, sizes
+
+  def cluster_labels_device(self, r_cut, plane="xyz", select=None, labels=None, sizes=None):
+    """The same for the resident points (set_positions(..., wall=False); rmb_cluster_labels_device), with the context's periods:
+    (labels, sizes), CUDA int32 tensors of n entries in the caller's order.  The sweep runs on the Morton-sorted copy and skips
+    tile pairs further apart than r_cut (options "force_sort", "force_cull"; under "xy" the gap ignores z), which changes no
+    label."""
+    n = int(self.n)
+    pl, select, labels, sizes = self._cluster_args(1, n, plane, select, labels, sizes, "cuda:%d" % self.device, (n,), "(n,)")
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_cluster_labels_device(self._h, ctypes.c_void_p(select.data_ptr()) if select is not None and select.numel() else None,
+                                                   float(r_cut), pl, ctypes.c_void_p(labels.data_ptr()) if labels.numel() else None,
+                                                   ctypes.c_void_p(sizes.data_ptr()) if sizes.numel() else None))
+    return labels, sizes
+
+  @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""
     try:

@@ -188,14 +188,15 @@ __device__ __forceinline__ void unit2_next(int order, int T, int& p, int& J) {
 // in a pseudo-periodic direction (L > 0) the pair force takes the nearest image of every separation
 // (d - rint(d/L) L, positions need not lie in one cell), so the interval is first moved by the multiple of L that
 // centres it: it then lies inside (-L, L), and |nearest image| over it is smallest at the end nearer to zero -- or
-// zero if the interval contains zero or is at least L long.
-__device__ __forceinline__ double tile_gap2(const double* bounds, int I, int J, double Lx = 0.0, double Ly = 0.0, double Lz = 0.0) {
+// zero if the interval contains zero or is at least L long.  `nd` = 2 leaves the z term out (distances taken in the plane).
+__device__ __forceinline__ double tile_gap2(const double* bounds, int I, int J, double Lx = 0.0, double Ly = 0.0, double Lz = 0.0, int nd = 3) {
   const double* bi = bounds + 6L * I;
   const double* bj = bounds + 6L * J;
   const double L[3] = {Lx, Ly, Lz};
   double g2 = 0.0;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
+    if (d >= nd) continue;
     double lo = bj[d] - bi[3 + d], hi = bj[3 + d] - bi[d];
     if (L[d] > 0.0) {
       if (hi - lo >= L[d]) { lo = 0.0; hi = 0.0; }

@@ -20,6 +20,9 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py --bond-order      bond_order_kernel / bond_order_finalize_kernel / pair_field_kernel (rmb_bond_order.hip) next to
                                                     pair_hist_kernel; `lds` is the static part, pair_field_kernel's accumulators add 12 n_bins
                                                     <= 49 152 bytes of dynamic LDS
+  python tools/kernel_resources.py --clusters        cluster_init_kernel / cluster_kernel / cluster_finish_kernel (rmb_clusters.hip) next to
+                                                    pair_hist_kernel; no dynamic LDS; scratch must be 0 (a spill in the union-find's loops
+                                                    would be the first thing to look at)
   python tools/kernel_resources.py --sym OTHER_TREE every kernel of the units that see pair_blocks.h / sym_kernels.h (symmetric families, fp32
                                                     twins, one-sided sweeps): OTHER_TREE | this tree, resources and every pair loop, differing
                                                     rows marked and counted -- what a change to the shared pair arithmetic touched
@@ -106,6 +109,7 @@ MSD_KERNELS = (("rmb_msd.hip", "msd_"),)
 SCATTERING_KERNELS = (("rmb_scattering.hip", "scat_"),)
 VAN_HOVE_KERNELS = (("rmb_van_hove.hip", "van_hove_"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
 BOND_ORDER_KERNELS = (("rmb_bond_order.hip", "bond_order_"), ("rmb_bond_order.hip", "pair_field_kernel"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
+CLUSTER_KERNELS = (("rmb_clusters.hip", "cluster_"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
 MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
 
 
@@ -179,6 +183,9 @@ if __name__ == "__main__":
     sys.exit(0)
   if "--bond-order" in sys.argv:
     potential_table(isa_stats.ROOT, BOND_ORDER_KERNELS)
+    sys.exit(0)
+  if "--clusters" in sys.argv:
+    potential_table(isa_stats.ROOT, CLUSTER_KERNELS)
     sys.exit(0)
   if "--pair-hist" in sys.argv:
     potential_table(isa_stats.ROOT, PAIR_HIST_KERNELS)
