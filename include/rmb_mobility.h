@@ -618,6 +618,30 @@ int rmb_cluster_labels_frames_device(rmb_ctx* ctx, const double* frames_dev, con
                                      const double* L, double r_cut, int plane, int* labels_dev, int* sizes_dev);
 int rmb_cluster_labels_device(rmb_ctx* ctx, const unsigned char* select_dev_or_null, double r_cut, int plane, int* labels_dev,
                               int* sizes_dev);
+/* Hydrodynamic function: the quadratic form of the translational pair mobility with plane waves,
+ *   H(k; e) = (1 / (N mu0)) sum_i sum_j e^T M_ij e cos(k . (x_i - x_j)),   mu0 = 1 / (6 pi eta a)
+ * (hydro_function_kernels.h).  M is the matrix of the tt product: RPY with the overlap patch; wall = 1: the single-wall block
+ * on heights clamped to a, every block damped by b_i b_j, b = z / a for z < a, exactly as rmb_set_positions(wall = 1) packs a
+ * configuration; mob_L: the three pseudo-periodic lengths of the mobility (<= 0: open; the 3^d images around the nearest one).
+ * Wavevectors as the scattering entries take them: kint = (K, 3) integers n and L = three lengths on the host,
+ * k = 2 pi n_d / L_d, the phase reduced in turns on the RAW coordinates.  pol = (K, 3) doubles on the host, the polarisation e
+ * of every wavevector (used as given; a unit vector for H).  Per frame f and wavevector m the two raw sums
+ *   out[f, m, 0] = S_self = sum_i b_i^2 e^T M_ii e            out[f, m, 1] = S_dist = 2 sum_{i<j} b_i b_j e^T M_ij e cos(theta_i - theta_j)
+ * are OVERWRITTEN, out_dev = (n_frames, K, 2) doubles: H = (S_self + S_dist) / (N mu0).  The pair block is built once per
+ * pair and contracted with eight wavevectors; no floating-point atomic: per-wave partial sums, added in a fixed order by a
+ * finishing launch -- the same call gives the same bits.  fp64, one radius, one device, asynchronous on the context's stream.
+ *   rmb_hydro_function_frames_device  n_frames frames of n points, frames_dev = (n_frames, n, 3) packed doubles on the device.
+ *                                     Nothing of the resident configuration is read or written.
+ *   rmb_hydro_function_device         the resident configuration with its own radius, boundary and periods (wall = 0 or 1; a
+ *                                     free-surface configuration or a target sub-range: RMB_ERR_STATE), one frame.
+ * RMB_ERR_ARG, before the device is touched: a null pointer (one whose array is empty may be null), negative sizes, K above
+ * 16384, |n_d| above 32768, a nonzero n_d along a direction with L_d <= 0, a radius or eta that is not positive and finite,
+ * wall not 0 or 1, a polarisation that is not finite, a mobility period that differs from the wavevector length of its
+ * direction (the phase factor of a pair would depend on the image).  RMB_ERR_STATE: option "precision" = 32.
+ * n_frames = 0 and K = 0 touch nothing; n = 0 gives zeros. */
+int rmb_hydro_function_frames_device(rmb_ctx* ctx, const double* frames_dev, long n_frames, long n, double a, double eta, int wall,
+                                     const double* mob_L, const double* L, const int* kint, const double* pol, long K, double* out_dev);
+int rmb_hydro_function_device(rmb_ctx* ctx, double eta, const double* L, const int* kint, const double* pol, long K, double* out_dev);
 /* Total potential energy of the resident configuration: the reference's equilibrium sampler's energy
  * (many_bodyMCMC/many_body_potential_pycuda.py:15-119), out = {U_one_blob, U_pair}; their sum is the reference's np.sum(U).
  * Uses the UNCLAMPED positions as rmb_blob_blob_force (rmb_set_positions with wall = 0; wall = 1 or a target sub-range:

@@ -24,6 +24,7 @@ callers built on the path, each mirroring the reference module of th
   scattering.py        IntermediateScattering: S(k), F(k, t), F_s(k, t) from the HIP Fourier sweeps, python -m rigidmultiblobswall_amd.scattering
   bondorder.py         BondOrder: psi_m, g_m(r), C_m(t) from the HIP neighbour and pair-field sweeps, python -m rigidmultiblobswall_amd.bondorder
   clusters.py          Clusters: cluster labels, sizes and size distribution from the HIP union-find sweep, python -m rigidmultiblobswall_amd.clusters
+  hydrofunction.py     HydrodynamicFunction: H(k), H_s, H / S from the HIP pair-block quadratic-form sweep, python -m rigidmultiblobswall_amd.hydrofunction
 """
 from . import _lib  # noqa: F401
 from .context import MobilityContext  # noqa: F401

@@ -100,6 +100,9 @@ SYMBOLS = {
                                                    _vp, _vp]),
     "rmb_cluster_labels_frames_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_long, ctypes.c_long, _vp, ctypes.c_double, ctypes.c_int, _vp, _vp]),
     "rmb_cluster_labels_device": (ctypes.c_int, [_vp, _vp, ctypes.c_double, ctypes.c_int, _vp, _vp]),
+    "rmb_hydro_function_frames_device": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                       _vp, _vp, _vp, _vp, ctypes.c_long, _vp]),
+    "rmb_hydro_function_device": (ctypes.c_int, [_vp, ctypes.c_double, _vp, _vp, _vp, ctypes.c_long, _vp]),
     "rmb_mcmc_propose_device": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_double, _vp, _vp, _vp]),
     "rmb_mcmc_body_delta_device": (ctypes.c_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp] + [ctypes.c_double] * 6 +

@@ -883,6 +883,63 @@ class MobilityContext(object):
     return labels, sizes
 
   @staticmethod
+  def _hydro_args(a, periodic_length, wavevectors, polarisation, in_plane, shard, nshards):
+    """Checks shared by the two hydrodynamic-function entries -> (L, kint (K, 3) int32, pol (K, 3) float64)."""
+    if in_plane:
+      raise ValueError("the hydrodynamic function has no in_plane variant")
+    if int(shard) != 0 or int(nshards) != 1:
+      raise ValueError("the hydrodynamic function does not take pair shards (shard = 0, nshards = 1)")
+    if a is not None and np.ndim(a) != 0:
+      raise ValueError("the hydrodynamic function takes one radius, not per-blob radii")
+    L, k = MobilityContext._scattering_wavevectors(periodic_length, wavevectors)
+    pol = np.ascontiguousarray(polarisation, dtype=np.float64)
+    if pol.shape != (k.shape[0], 3):
+      raise ValueError("polarisation must be a float array of shape (K, 3), one vector per wavevector")
+    return L, k, pol
+
+  def hydrodynamic_function_frames_device(self, frames, a, eta, periodic_length, wavevectors, polarisation, wall=True,
+                                          mobility_periodic_length=None, out=None, in_plane=False, shard=0, nshards=1):
+    """Raw sums behind the hydrodynamic function H(k; e) = (1 / (N mu0)) sum_ij e^T M_ij e cos(k . (x_i - x_j)) of every frame of
+    `frames`, a contiguous CUDA float64 tensor (n_frames, n, 3) (rmb_hydro_function_frames_device).  M is the matrix of the tt
+    product for blobs of radius `a` in a fluid of viscosity `eta`: wall=True the single-wall block (heights clamped to a, blobs
+    below a damped by z / a, as set_positions packs them), False the unbounded RPY block; mobility_periodic_length: the three
+    pseudo-periodic lengths of the mobility (None or <= 0: open).  wavevectors: integer array (K, 3) of n, k = 2 pi n_d /
+    L_d with periodic_length = the three L_d, as density_modes_frames_device; where the mobility is periodic its period must be
+    that L_d.  polarisation: (K, 3) floats, the vector e of every wavevector (hydrofunction.polarisations makes unit vectors).
+    Returns a CUDA float64 tensor (n_frames, K, 2) of (S_self, S_dist) = (sum_i b_i^2 e^T M_ii e, 2 sum_{i<j} b_i b_j e^T M_ij e
+    cos(theta_i - theta_j)); out= (that shape, contiguous) is OVERWRITTEN.  H = (S_self + S_dist) 6 pi eta a / n.  The same
+    call gives the same bits.  fp64, one radius; no in_plane variant, no pair shards, no free surface.  Asynchronous on torch's
+    stream; the resident configuration is neither read nor changed."""
+    if isinstance(wall, str):
+      raise ValueError("the hydrodynamic function knows a no-slip wall (True) or none (False), not %r" % (wall,))
+    n_frames, n = self._scattering_frames(frames)
+    L, k, pol = self._hydro_args(a, periodic_length, wavevectors, polarisation, in_plane, shard, nshards)
+    mob_L = _as_f64(np.zeros(3) if mobility_periodic_length is None else mobility_periodic_length, 3)
+    K = int(k.shape[0])
+    out = _cuda_out(out, (n_frames, K, 2), "(n_frames, K, 2)", "float64", frames.device, zero=False)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_hydro_function_frames_device(self._h, ctypes.c_void_p(frames.data_ptr()) if frames.numel() else None, n_frames, n,
+                                                          float(a), float(eta), int(bool(wall)), _ptr(mob_L), _ptr(L),
+                                                          ctypes.c_void_p(k.ctypes.data) if K else None,
+                                                          ctypes.c_void_p(pol.ctypes.data) if K else None, K,
+                                                          ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out
+
+  def hydrodynamic_function(self, eta, periodic_length, wavevectors, polarisation, in_plane=False, shard=0, nshards=1):
+    """The same two sums for the resident configuration (set_positions with wall True or False), with its own radius, boundary
+    and periods, through the same kernel as one frame (rmb_hydro_function_device): a numpy array (K, 2).  Synchronous.  A
+    free-surface configuration, a target sub-range and option "precision" = 32 are refused."""
+    import torch
+    L, k, pol = self._hydro_args(None, periodic_length, wavevectors, polarisation, in_plane, shard, nshards)
+    K = int(k.shape[0])
+    out = torch.empty((K, 2), dtype=torch.float64, device="cuda:%d" % self.device)
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_hydro_function_device(self._h, float(eta), _ptr(L), ctypes.c_void_p(k.ctypes.data) if K else None,
+                                                   ctypes.c_void_p(pol.ctypes.data) if K else None, K,
+                                                   ctypes.c_void_p(out.data_ptr()) if out.numel() else None))
+    return out.cpu().numpy()
+
+  @staticmethod
   def _body_law(body_potential):
     """(eps, b) of the body_potential= keyword of the single-body moves, as two floats."""
     try:

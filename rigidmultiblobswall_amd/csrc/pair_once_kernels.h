@@ -27,13 +27,28 @@
 //   pair<GUARDED>(a, st, self, q, take) one pair; `take` is true in the loop and lane < 32 at the peeled step
 // Padding (the lanes past n of a partial last tile) is staged as points 2e100 apart with .w = PAD_W; pair() must make
 // nothing of them.
+// A policy that declares `static constexpr bool SLOTS = true` keeps per-point data of its own next to the records (the
+// hydrodynamic function's phase factors, hydro_function_kernels.h) and per-chunk sums.  It supplies, on top of the above:
+//   row(a, st, self, valid)             once per fetch of the lane's own point (tile I changed)
+//   stage(a, st, p, lane, diag)         the record p has just gone into slot `lane`: fill the policy's own slab, same slot
+//   pair<GUARDED>(a, st, self, q, take, slot)   pair() with the slot q was read from
+//   flush(a, st, chunk)                 the steps of chunk `chunk` are done; once per chunk
+// and its chunks are cut PER FRAME: a.spw steps each (always given, never the one-range-per-wave default), a.chunks_per_frame
+// = ceil(steps of a frame / a.spw) of them in every frame, the last one short; chunk c is piece c % chunks_per_frame of frame
+// c / chunks_per_frame.  No chunk reaches into the next frame, and how a frame is cut does not depend on the frames around it.
+// Policies without SLOTS compile to what they were: every use below is an `if constexpr`.
 // The walk below stays its own loop, not sym_walk (sym_walk.h): FRAMES needs a hook at the unit advance that no other sweep uses.
 #pragma once
 #include "pair_ops.h"
 #include "sym_schedule.h"
 #include "sym_walk.h"
 
+#include <type_traits>
+
 namespace rmb {
+
+template <class OP, class = void> struct PairOnceSlots : std::false_type {};
+template <class OP> struct PairOnceSlots<OP, std::void_t<decltype(OP::SLOTS)>> : std::bool_constant<OP::SLOTS> {};
 
 // The fields the frame reads; fill_sym_args (rmb_internal.h) fills them by name.
 struct PairOnceArgs {
@@ -66,11 +81,13 @@ __device__ __forceinline__ void pair_once_steps(const typename OP::Args& a, type
                                                 int lane, int kb, int kl, bool peel) {
   for (int k = kb; k < kl; ++k) {
     const double4 q = rec[(lane + k) & 63];
-    OP::template pair<GUARDED>(a, st, self, q, true);
+    if constexpr (PairOnceSlots<OP>::value) OP::template pair<GUARDED>(a, st, self, q, true, (lane + k) & 63);
+    else                                    OP::template pair<GUARDED>(a, st, self, q, true);
   }
   if (peel) {
     const double4 q = rec[(lane + 32) & 63];
-    OP::template pair<GUARDED>(a, st, self, q, lane < 32);
+    if constexpr (PairOnceSlots<OP>::value) OP::template pair<GUARDED>(a, st, self, q, lane < 32, (lane + 32) & 63);
+    else                                    OP::template pair<GUARDED>(a, st, self, q, lane < 32);
   }
 }
 
@@ -80,11 +97,19 @@ __device__ __forceinline__ void pair_once_sweep(const typename OP::Args& a, type
   const int lane = threadIdx.x & 63;
   const long n_waves = sym_n_waves();
   const long w = pair_once_wave(a);
-  const long spw = a.chunk_steps > 0 ? a.chunk_steps : (a.step_end + n_waves - 1) / n_waves;
+  long spw;
+  if constexpr (PairOnceSlots<OP>::value) spw = a.spw;
+  else spw = a.chunk_steps > 0 ? a.chunk_steps : (a.step_end + n_waves - 1) / n_waves;
   for (long chunk = w;; chunk += n_waves) {
     long s = chunk * spw;
-    if (s >= a.step_end) break;
     long s_end = s + spw;
+    if constexpr (PairOnceSlots<OP>::value) {      // piece chunk % chunks_per_frame of frame chunk / chunks_per_frame
+      const long f = chunk / a.chunks_per_frame, spf = a.units_per_frame * 64;
+      s = f * spf + (chunk - f * a.chunks_per_frame) * spw;
+      s_end = s + spw;
+      if (s_end > (f + 1) * spf) s_end = (f + 1) * spf;
+    }
+    if (s >= a.step_end) break;
     if (s_end > a.step_end) s_end = a.step_end;
     int I = 0, J = 0;
     long frame = 0;
@@ -111,14 +136,17 @@ __device__ __forceinline__ void pair_once_sweep(const typename OP::Args& a, type
           vi_ok = i < a.n;
           self = make_double4(1e100, 1e100, 1e100, OP::PAD_W);
           if (vi_ok) self = OP::fetch(a, frame, i);
+          if constexpr (PairOnceSlots<OP>::value) OP::row(a, st, self, vi_ok);
         }
         if (!diag) {
           const long j = 64L * J + lane;
           double4 p = make_double4(-1e100, -1e100, -1e100, OP::PAD_W);
           if (j < a.n) p = OP::fetch(a, frame, j);
           rec[lane] = p;
+          if constexpr (PairOnceSlots<OP>::value) OP::stage(a, st, p, lane, false);
         } else {
           rec[lane] = make_double4(vi_ok ? self.x : -1e100, vi_ok ? self.y : -1e100, vi_ok ? self.z : -1e100, self.w);
+          if constexpr (PairOnceSlots<OP>::value) OP::stage(a, st, self, lane, true);
           if (k0 == 0) OP::diag_start(a, st, self, vi_ok);
         }
         wave_lds_sync();
@@ -138,6 +166,7 @@ __device__ __forceinline__ void pair_once_sweep(const typename OP::Args& a, type
         }
       }
     }
+    if constexpr (PairOnceSlots<OP>::value) OP::flush(a, st, chunk);
   }
 }
 

@@ -42,6 +42,10 @@
 //   rmb_clusters.hip  connected components of the bond graph (cluster_kernels.h: a policy of the pair-once frame whose pair term
 //                    is a lock-free union-find in global memory), of caller-owned frames and of the resident raw positions:
 //                    init, sweep and finishing launch
+//   rmb_hydro_function.hip  the hydrodynamic function H(k) (hydro_function_kernels.h: a policy of the pair-once frame that keeps
+//                    the phase factors of the staged tile in a second LDS slab; the tt pair block built once per pair and
+//                    contracted with a chunk of wavevectors), of caller-owned frames and of the resident configuration:
+//                    coefficients, sweep on a (walk, wavevector chunk) grid, finishing launch
 //   pair_table_kernels.h (a header) the tabulated radial pair law: what TableLaw of the force sweep (rmb_sym.hip) and the TABLE
 //                    instances of the energy sweep (rmb_potential.hip) share -- LDS staging, interval lookup, the two cubics;
 //                    rmb_ctx_set_pair_table and the force entry points are in rmb_entry.hip
@@ -115,6 +119,7 @@ struct CtxBuffers {
   DevBuf scat_ws;          // scattering (rmb_scattering.hip): n / L of the wavevectors, series-major records, partial sums
   DevBuf vh_ws;            // van Hove self sweep (rmb_van_hove.hip): per-workgroup partial moments
   DevBuf cluster_ws;       // cluster labels (rmb_clusters.hip): the parent array of the union-find
+  DevBuf hydro_ws;         // hydrodynamic function (rmb_hydro_function.hip): n / L and e6 of the wavevectors, per-chunk partial sums
   DevBuf pair_table;       // records (c0, c1, c2, c3) of the tabulated pair law (rmb_ctx_set_pair_table)
   DevBuf det_ws;           // per-unit partials of the deterministic symmetric pass
   DevBuf wave_clock;  // optional per-wave (start, end) wall-clock stamps of the symmetric kernel
@@ -125,7 +130,7 @@ struct CtxBuffers {
 using CB = CtxBuffers;
 constexpr DevBuf CB::* kCtxBufs[] = {&CB::pos, &CB::r_stage, &CB::vec, &CB::vec2, &CB::out, &CB::partial, &CB::tmp3n, &CB::tile_bounds,
                                      &CB::fpos, &CB::fperm, &CB::fsort_keys, &CB::fsort_vals, &CB::fsort_tmp, &CB::fsort_box,
-                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::vh_ws, &CB::cluster_ws, &CB::pair_table, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
+                                     &CB::pot_ws, &CB::mcmc_ws, &CB::msd_ws, &CB::scat_ws, &CB::vh_ws, &CB::cluster_ws, &CB::hydro_ws, &CB::pair_table, &CB::det_ws, &CB::wave_clock, &CB::krylov, &CB::symbuf};      // + st[8]
 static_assert(sizeof(CtxBuffers) == (sizeof(kCtxBufs) / sizeof(kCtxBufs[0]) + 8) * sizeof(DevBuf),
               "a DevBuf of CtxBuffers is missing from kCtxBufs (or st[] changed its length)");
 template <class Bufs, class F>      // Bufs: CtxBuffers or const CtxBuffers (an rmb_ctx converts)

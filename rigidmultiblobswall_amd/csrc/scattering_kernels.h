@@ -33,6 +33,7 @@
 // No floating-point atomic anywhere: the same call gives the same bits.
 #pragma once
 #include "lag_sweep_kernels.h"
+#include "scat_phase.h"      // scat_phase: (cos theta, sin theta) of a point
 
 namespace rmb {
 
@@ -70,13 +71,6 @@ struct ScatSweepArgs : LagSweepArgs {      // B: points; 1 for the collective su
   double* sums;            // (n_lags, K), added to
   long K, k0, k_count;     // row y, component c is wavevector k0 + y NC + c; k_count of them in all
 };
-
-// (cos theta, sin theta) of a point for the wavevector with c = n / L
-__device__ __forceinline__ void scat_phase(double x, double y, double z, double cx, double cy, double cz, double* s, double* c) {
-  const double t = __builtin_fma(z, cz, __builtin_fma(y, cy, x * cx));
-  const double r = t - __builtin_rint(t);
-  sincospi(r + r, s, c);
-}
 
 __global__ __launch_bounds__(kScatCoefBatch) void scat_coef_kernel(const ScatCoefArgs a) {
   const long i = threadIdx.x;

@@ -20,6 +20,7 @@ residency, so a change that moves an instance across a register or LDS boundary 
   python tools/kernel_resources.py --bond-order      bond_order_kernel / bond_order_finalize_kernel / pair_field_kernel (rmb_bond_order.hip) next to
                                                     pair_hist_kernel; `lds` is the static part, pair_field_kernel's accumulators add 12 n_bins
                                                     <= 49 152 bytes of dynamic LDS
+  python tools/kernel_resources.py --hydro-function  hydro_coef_kernel / hydro_self_kernel / hydro_function_kernel / hydro_finish_kernel (rmb_hydro_function.hip)
   python tools/kernel_resources.py --clusters        cluster_init_kernel / cluster_kernel / cluster_finish_kernel (rmb_clusters.hip) next to
                                                     pair_hist_kernel; no dynamic LDS; scratch must be 0 (a spill in the union-find's loops
                                                     would be the first thing to look at)
@@ -110,6 +111,7 @@ SCATTERING_KERNELS = (("rmb_scattering.hip", "scat_"),)
 VAN_HOVE_KERNELS = (("rmb_van_hove.hip", "van_hove_"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
 BOND_ORDER_KERNELS = (("rmb_bond_order.hip", "bond_order_"), ("rmb_bond_order.hip", "pair_field_kernel"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
 CLUSTER_KERNELS = (("rmb_clusters.hip", "cluster_"), ("rmb_pair_hist.hip", "pair_hist_kernel"))
+HYDRO_FUNCTION_KERNELS = (("rmb_hydro_function.hip", "hydro_"),)
 MOVE_KERNELS = (("rmb_mcmc_moves.hip", "body_delta_kernel"), ("rmb_mcmc_moves.hip", "move_finish_kernel"))
 
 
@@ -186,6 +188,9 @@ if __name__ == "__main__":
     sys.exit(0)
   if "--clusters" in sys.argv:
     potential_table(isa_stats.ROOT, CLUSTER_KERNELS)
+    sys.exit(0)
+  if "--hydro-function" in sys.argv:
+    potential_table(isa_stats.ROOT, HYDRO_FUNCTION_KERNELS)
     sys.exit(0)
   if "--pair-hist" in sys.argv:
     potential_table(isa_stats.ROOT, PAIR_HIST_KERNELS)
