@@ -196,7 +196,9 @@ int rmb_ctx_release_stream(rmb_ctx* ctx);
 int rmb_ctx_set_option(rmb_ctx* ctx, const char* key, long value);
 /* Current value of an option (same keys, same table); lets a caller switch one temporarily and restore what was there.  Read-only
  * key "last_path": the kernel family of the last product (0 one-sided sweep, 1 symmetric per wave, 2 deterministic
- * symmetric, 3 symmetric workgroup-cooperative, 4 symmetric with two target blobs per lane). */
+ * symmetric, 3 symmetric workgroup-cooperative, 4 symmetric with two target blobs per lane).  Read-only key
+ * "last_krylov_partials": the first-pass partials per basis row that a finishing launch left for the last Gram-Schmidt step
+ * (the body count, or the count of 64-blob tiles for the plain Lanczos step); 0 = the step ran its own dots launch. */
 int rmb_ctx_get_option(rmb_ctx* ctx, const char* key, long* value);
 
 /* Upload / pack positions: fuses shift_heights + damping_matrix_B (mobility.py:52-84).
@@ -326,6 +328,27 @@ int rmb_rigid_operator_device(rmb_ctx* ctx, long n_bodies, long n_b, const doubl
 int rmb_rigid_arnoldi_step_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* A11_dev, const double* A12_dev,
                                   const double* A21_dev, const double* A22_dev, const double* K_dev, double* V_dev, long ldv, long j,
                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev);
+/* Single steps in the forms the native loops below run, for the step-level tests (tests/test_gpu_krylov.py): each entry
+ * enqueues the launches of ONE iteration and returns -- no loop, no wait.
+ * rmb_rigid_arnoldi_step2_device: the step above with the loop's two flags.  z_ready != 0: z_dev already holds P^-1 v_j (the
+ *   previous step's last launch left it there), the block launch is skipped; fuse_pc != 0: the Gram-Schmidt ending also writes
+ *   z_dev = P^-1 v_{j+1}, and -- with the symmetric sweep, option gmres_fuse_dots and up to 256 bodies -- the operator's
+ *   finishing launch takes the first pass's dots as one partial per body.  The ending is the low-synchronisation one (option
+ *   krylov_low_sync, on by default).
+ * rmb_rigid_lanczos_step_device: one iteration of rmb_rigid_lanczos_device: pv = P v_i (skipped when pv_ready != 0), mw = the
+ *   sweep's result, d = P^T M pv orthogonalised in place against v_0 .. v_i, h_ii and h_{i+1,i} in col[i], col[i + 1],
+ *   v_{i+1} = row i + 1 of V; fuse_next != 0: the ending also leaves P v_{i+1} in pv_dev (d_dev must then differ from pv_dev).
+ * rmb_lanczos_step_device: one iteration of rmb_lanczos_device: x1 = M v_i (product, in_plane as there; 3 N doubles, 6 N for
+ *   the grand mobility), orthogonalised in place, column and v_{i+1} as above.  V_dev: rows of ldv >= 3 N (6 N) doubles. */
+int rmb_rigid_arnoldi_step2_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* A11_dev, const double* A12_dev,
+                                   const double* A21_dev, const double* A22_dev, const double* K_dev, double* V_dev, long ldv, long j,
+                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev, int z_ready,
+                                   int fuse_pc);
+int rmb_rigid_lanczos_step_device(rmb_ctx* ctx, long n_bodies, long n_b, const double* Linv_dev, double* V_dev, long ldv, long i,
+                                  double eta, double* pv_dev, double* mw_dev, double* d_dev, double* col_dev, double* col_mapped_dev,
+                                  int pv_ready, int fuse_next);
+int rmb_lanczos_step_device(rmb_ctx* ctx, int product, int in_plane, double* V_dev, long ldv, long i, double eta, double* x1_dev,
+                            double* col_dev, double* col_mapped_dev);
 /* The whole right-preconditioned GMRES(restart) of [[M, -K], [-K^T, 0]] x = b (quaternion_integrator_multi_bodies.py:1441-1547
  * -> general_application_utils.py:608-627 -> scipy; all bodies free, one body shape) as ONE call: per iteration one
  * rmb_rigid_arnoldi_step_device and an event; the Givens rotations and the convergence test run on the host INSIDE the
@@ -389,6 +412,19 @@ int rmb_krylov_orthogonalize_device(rmb_ctx* ctx, long n, long rows, const doubl
  * no copy command. */
 int rmb_krylov_orthogonalize2_device(rmb_ctx* ctx, long n, long rows, const double* V_dev, long ldv, double* w_dev,
                                      double* col_dev, double* v_next_dev, double* col_mapped_dev);
+/* Any form of the Gram-Schmidt ending on caller-chosen V and w.  low_sync != 0 (and option krylov_low_sync): three launches,
+ * the last one subtracts the second projection, takes |w| = sqrt(|w1|^2 - |h2|^2) and normalises; otherwise the four launches
+ * above.  z_dev != NULL: the vector is laid out as [n_bodies x r1; n_bodies x r2], n_bodies (r1 + r2) = n, and the last launch
+ * (workgroup = body) also writes z = blocks * v_next: z1_b = A11_b v1_b + A12_b v2_b, z2_b = A21_b v1_b + A22_b v2_b with the
+ * square blocks addressed as in rmb_block_apply_device (NULL = zero block).  z_dev == NULL: the body arguments are ignored. */
+int rmb_krylov_orthogonalize3_device(rmb_ctx* ctx, long n, long rows, const double* V_dev, long ldv, double* w_dev,
+                                     double* col_dev, double* v_next_dev, double* col_mapped_dev, int low_sync, long n_bodies,
+                                     long r1, long r2, const rmb_block* a11, const rmb_block* a12, const rmb_block* a21,
+                                     const rmb_block* a22, double* z_dev);
+/* The two vector launches of the native loops: y[e] += sum_{i < k} coef[i] V[i][e] for e < n (k <= 256; coef_dev: k doubles the
+ * device can read, mapped host memory in the loops), and *out_dev = |v| over n doubles (one workgroup, fixed order). */
+int rmb_krylov_lincomb_device(rmb_ctx* ctx, double* y_dev, const double* V_dev, long ldv, const double* coef_dev, long k, long n);
+int rmb_krylov_norm_device(rmb_ctx* ctx, const double* v_dev, long n, double* out_dev);
 /* Page-locked host memory mapped into the device's address space (hipHostMallocMapped), zero-filled: *host = the address
  * the host reads / writes, *dev = the address kernels use.  Freed with rmb_host_mapped_free(host). */
 int rmb_host_mapped_alloc(size_t bytes, void** host, void** dev);

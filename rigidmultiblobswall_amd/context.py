@@ -367,6 +367,77 @@ class MobilityContext(object):
     _lib.check(self._lib.rmb_rigid_arnoldi_step_device(self._h, nb, n_b, p(A11), p(A12), p(A21), p(A22), p(K), p(V), V.stride(0), int(j),
                                                        float(eta), p(z), p(w), p(col), ctypes.c_void_p(col_mapped) if col_mapped else None))
 
+  # ---- single steps of the native loops (the step-level tests): each enqueues one iteration's launches and returns --------
+  def krylov_orthogonalize3_device(self, V, rows, w, col, v_next, col_mapped=0, low_sync=True, blocks=None, z=None, r1=0, r2=0,
+                                   transpose=(False,) * 4):
+    """Any form of the Gram-Schmidt ending (rmb_krylov_orthogonalize3_device): as krylov_orthogonalize_device, with the
+    low-synchronisation ending when low_sync, and -- z given -- z = blocks * v_next written by the last launch: blocks =
+    (a11, a12, a21, a22) of (n_bodies, r, c) tensors or None, the vector laid out as [n_bodies x r1; n_bodies x r2].
+    V: (m, n) view with unit column stride (the row stride may exceed n)."""
+    n = w.numel()
+    assert V.stride(1) == 1 and w.is_contiguous() and col.is_contiguous() and v_next.is_contiguous()
+    refs, nb = [None] * 4, 0
+    if z is not None:
+      assert z.is_contiguous()
+      keep = [self._block(t, tr) for t, tr in zip(blocks, transpose)]
+      refs = [ctypes.byref(b) if b is not None else None for b in keep]
+      nb = n // (r1 + r2) if r1 + r2 > 0 and n % (r1 + r2) == 0 else 0
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_krylov_orthogonalize3_device(self._h, n, int(rows), ctypes.c_void_p(V.data_ptr()), V.stride(0),
+                                                          ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(col.data_ptr()),
+                                                          ctypes.c_void_p(v_next.data_ptr()), ctypes.c_void_p(col_mapped) if col_mapped else None,
+                                                          int(bool(low_sync)), nb, int(r1), int(r2), refs[0], refs[1], refs[2], refs[3],
+                                                          ctypes.c_void_p(z.data_ptr()) if z is not None else None))
+
+  def krylov_lincomb_device(self, y, V, coef, k):
+    """y += V[:k]^T coef in one launch (rmb_krylov_lincomb_device); V: (m, n) view with unit column stride, k <= 256."""
+    assert V.stride(1) == 1 and y.is_contiguous() and coef.is_contiguous()
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_krylov_lincomb_device(self._h, ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(V.data_ptr()), V.stride(0),
+                                                   ctypes.c_void_p(coef.data_ptr()), int(k), y.numel()))
+
+  def krylov_norm_device(self, v, out):
+    """out[0] = |v| in one launch of one workgroup (rmb_krylov_norm_device)."""
+    assert v.is_contiguous() and out.is_contiguous()
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_krylov_norm_device(self._h, ctypes.c_void_p(v.data_ptr()), v.numel(), ctypes.c_void_p(out.data_ptr())))
+
+  def rigid_arnoldi_step2_device(self, A11, A12, A21, A22, K, V, j, eta, z, w, col, col_mapped=0, z_ready=False, fuse_pc=False):
+    """rigid_arnoldi_step_device in the native loop's forms (rmb_rigid_arnoldi_step2_device): z_ready -- z already holds
+    P^-1 V[j]; fuse_pc -- the ending also leaves P^-1 V[j + 1] in z."""
+    nb, n_b = K.shape[0], K.shape[1] // 3
+    for t in (A11, A12, A21, A22, K, z, w, col):
+      assert t.is_contiguous()
+    assert V.stride(1) == 1
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_rigid_arnoldi_step2_device(self._h, nb, n_b, p(A11), p(A12), p(A21), p(A22), p(K), p(V), V.stride(0), int(j),
+                                                        float(eta), p(z), p(w), p(col), ctypes.c_void_p(col_mapped) if col_mapped else None,
+                                                        int(bool(z_ready)), int(bool(fuse_pc))))
+
+  def rigid_lanczos_step_device(self, Linv, V, i, eta, pv, mw, d, col, col_mapped=0, pv_ready=False, fuse_next=False):
+    """One iteration of rigid_lanczos_device's loop (rmb_rigid_lanczos_step_device): pv = P V[i] (unless pv_ready), mw = the
+    sweep's result, d = P^T M pv orthogonalised against V[:i + 1], V[i + 1] = d / |d|; fuse_next: pv = P V[i + 1] after it."""
+    nb, n_b = Linv.shape[0], Linv.shape[1] // 3
+    for t in (Linv, pv, mw, d, col):
+      assert t.is_contiguous()
+    assert V.stride(1) == 1
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_rigid_lanczos_step_device(self._h, nb, n_b, p(Linv), p(V), V.stride(0), int(i), float(eta), p(pv), p(mw), p(d),
+                                                       p(col), ctypes.c_void_p(col_mapped) if col_mapped else None, int(bool(pv_ready)),
+                                                       int(bool(fuse_next))))
+
+  def lanczos_step_device(self, product, V, i, eta, x1, col, col_mapped=0, in_plane=False):
+    """One iteration of lanczos_device's loop (rmb_lanczos_step_device): x1 = M V[i] for product "tt" / "grand", orthogonalised
+    against V[:i + 1], V[i + 1] = x1 / |x1|."""
+    assert V.stride(1) == 1 and x1.is_contiguous() and col.is_contiguous()
+    code = product if isinstance(product, int) else {"tt": 0, "grand": 1}[product]
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    self._follow_torch_stream()
+    _lib.check(self._lib.rmb_lanczos_step_device(self._h, code, int(bool(in_plane)), p(V), V.stride(0), int(i), float(eta), p(x1), p(col),
+                                                 ctypes.c_void_p(col_mapped) if col_mapped else None))
+
   def rigid_gmres_device(self, A11, A12, A21, A22, K, b, tol, restart, maxiter, eta):
     """The whole right-preconditioned GMRES of the rigid-body problem in one library call (rmb_rigid_gmres_device); b is
     the RAW right-hand side (scaled to unit norm inside, the solution scaled back).  Returns (x tensor, info dict as

@@ -251,6 +251,7 @@ int rmb_ctx_get_option(rmb_ctx* c, const char* key, long* value) {
   // read-only: which kernel family the last product ran on (0 one-sided sweep, 1 symmetric per-wave, 2 deterministic
   // symmetric, 3 symmetric workgroup-cooperative)
   if (!strcmp(key, "last_path")) { *value = c->last_path; return 0; }
+  if (!strcmp(key, "last_krylov_partials")) { *value = c->last_krylov_partials; return 0; }
   if (!strcmp(key, "diagnostics_build")) { *value = kDiagnosticsBuild; return 0; }
   // read-only: a hash of the addresses of every device buffer the library owns for this context (CtxBuffers).  A captured
   // hipGraph of device-path calls holds those addresses by value; it stays valid exactly while this number is unchanged (a

@@ -87,6 +87,18 @@ __global__ __launch_bounds__(kVecT) void vec_div_kernel(double* out, const doubl
 
 inline unsigned blocks_of(long n) { return (unsigned)((n + kVecT - 1) / kVecT); }
 
+// the two launches the loops and the exported step entries (rmb_krylov_lincomb_device, rmb_krylov_norm_device) share
+inline int launch_lincomb(rmb_ctx* c, double* y, const double* V, long ldv, const double* coef, long k, long n) {
+  hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(n)), dim3(kVecT), 0, c->stream, y, V, ldv, coef, (int)k, n);
+  RMB_HIP(hipGetLastError());
+  return 0;
+}
+inline int launch_norm(rmb_ctx* c, const double* v, long n, double* out) {
+  hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, c->stream, v, n, out);
+  RMB_HIP(hipGetLastError());
+  return 0;
+}
+
 // Square-root function of a symmetric tridiagonal matrix applied to e_1, by QL sweeps with implicit Wilkinson shifts (the classical
 // tql2 scheme) WITHOUT accumulating the eigenvector matrix: T = Q L Q^T with Q = G_1 G_2 ... G_m a product of plane rotations,
 // so  f(T) e_1 = Q (f(L) Q^T e_1)  needs the first ROW of Q -- carried along in O(1) per rotation -- and then the rotations
@@ -261,8 +273,7 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
   long n_products = 0;
 
   auto host_norm = [&](const double* v, double* out) -> int {
-    hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, v, n, ws.hscal_dev);
-    RMB_HIP(hipGetLastError());
+    if (int rc = launch_norm(c, v, n, ws.hscal_dev)) return rc;
     RMB_HIP(hipStreamSynchronize(s));
     *out = *ws.hscal;
     return 0;
@@ -373,8 +384,7 @@ int rmb_rigid_gmres_device(rmb_ctx* c, long n_bodies, long n_b, const double* A1
         for (long q = i + 1; q < k_used; ++q) t -= H[(size_t)i * m_max + q] * ws.hcoef[q];
         ws.hcoef[i] = t / H[(size_t)i * m_max + i];
       }
-      hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(n)), dim3(kVecT), 0, s, y, V, ldv, ws.hcoef_dev, (int)k_used, n);
-      RMB_HIP(hipGetLastError());
+      if (int rc = launch_lincomb(c, y, V, ldv, ws.hcoef_dev, k_used, n)) return rc;
       // (no wait here: the host writes hcoef again only after it has waited for an event of a LATER step of this stream --
       //  of the next cycle, or of the next call on this context -- and by then this kernel has run)
     }
@@ -439,8 +449,7 @@ int lanczos_loop(rmb_ctx* c, long dim, const double* z_dev, double factor, doubl
     return 0;
   };
 
-  hipLaunchKernelGGL(vec_norm_kernel, dim3(1), dim3(1024), 0, s, z_dev, dim, b.hscal_dev);
-  RMB_HIP(hipGetLastError());
+  if (int rc = launch_norm(c, z_dev, dim, b.hscal_dev)) return rc;
   RMB_HIP(hipStreamSynchronize(s));
   const double v_norm = *b.hscal;
   if (!(v_norm > 0.0) || !std::isfinite(v_norm)) return give_up(1);
@@ -496,14 +505,32 @@ int lanczos_loop(rmb_ctx* c, long dim, const double* z_dev, double factor, doubl
   const long k = (long)coef.size();
   memcpy(b.hcoef, coef.data(), (size_t)k * sizeof(double));
   hipLaunchKernelGGL(vec_zero_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.work(1), dim);
-  hipLaunchKernelGGL(vec_lincomb_kernel, dim3(blocks_of(dim)), dim3(kVecT), 0, s, b.work(1), b.V, dim, b.hcoef_dev, (int)k, dim);
   RMB_HIP(hipGetLastError());
+  if (int rc = launch_lincomb(c, b.work(1), b.V, dim, b.hcoef_dev, k, dim)) return rc;
   if (int rc = finish_result(b.work(1))) return rc;
   // (no wait: whoever writes hcoef next -- a Lanczos entry or rmb_rigid_gmres_device -- has by then waited for an event recorded
   //  later on this stream; the result is enqueued, the scalars are final)
   *iterations = its;
   if (products) *products = n_products;
   return 0;
+}
+// One step of the plain forcing's loop (rmb_lanczos_device, rmb_lanczos_step_device): x1 = M v_i, orthogonalised in place against
+// v_0 .. v_i in the low-synchronisation form, v_{i+1} = row i + 1 of V.  The arguments have been checked by the caller.
+int plain_lanczos_step(rmb_ctx* c, int product, int in_plane, double* V, long ldv, long i, double eta, double* x1, double* col, double* col_mapped) {
+  const long n3 = 3 * c->n, dim = product == 1 ? 2 * n3 : n3;
+  const double* v = V + i * ldv;
+  long tiles = 0;
+  if (product == 0 && !in_plane) {
+    // (small decks: the finishing launch also takes the first Gram-Schmidt pass's dots, five launches per iteration)
+    if (int rc = plain_tt_with_dots(c, v, eta, x1, V, ldv, i + 1, &tiles)) return rc;
+  } else if (product == 0) {
+    if (int rc = matvec_device_impl(c, rmb::KIND_TT, 1, v, nullptr, eta, x1)) return rc;
+  } else {
+    const double* in[2] = {v, v + n3};
+    double* out[2] = {x1, x1 + n3};
+    if (int rc = rmb_matvec_op_device(c, RMB_OP_GRAND, 0, 2, in, 2, out, eta)) return rc;
+  }
+  return krylov_orthogonalize_impl(c, dim, i + 1, V, ldv, x1, col, V + (i + 1) * ldv, col_mapped, nullptr, tiles, true);
 }
 }  // namespace
 }  // namespace rmbi
@@ -552,27 +579,44 @@ int rmb_lanczos_device(rmb_ctx* c, int product, int in_plane, const double* z_de
   RMB_HIP(hipSetDevice(c->device));
   const long n3 = 3 * c->n, dim = product == 1 ? 2 * n3 : n3;
   auto step = [&](long i, const KrylovWs& b) -> int {
-    const double* v = b.V + i * dim;
-    double* const x1 = b.work(1);
-    long tiles = 0;
-    if (product == 0 && !in_plane) {
-      // (small decks: the finishing launch also takes the first Gram-Schmidt pass's dots, five launches per iteration)
-      if (int rc = plain_tt_with_dots(c, v, eta, x1, b.V, dim, i + 1, &tiles)) return rc;
-    } else if (product == 0) {
-      if (int rc = matvec_device_impl(c, rmb::KIND_TT, 1, v, nullptr, eta, x1)) return rc;
-    } else {
-      const double* in[2] = {v, v + n3};
-      double* out[2] = {x1, x1 + n3};
-      if (int rc = rmb_matvec_op_device(c, RMB_OP_GRAND, 0, 2, in, 2, out, eta)) return rc;
-    }
-    return krylov_orthogonalize_impl(c, dim, i + 1, b.V, dim, x1, b.cols + (size_t)i * b.col_row, b.V + (i + 1) * dim,
-                                     b.hcols_dev + (size_t)i * b.col_row, nullptr, tiles, true);
+    return plain_lanczos_step(c, product, in_plane, b.V, dim, i, eta, b.work(1), b.cols + (size_t)i * b.col_row, b.hcols_dev + (size_t)i * b.col_row);
   };
   auto result = [&](double* combo) -> int {
     RMB_HIP(hipMemcpyAsync(noise_dev, combo, (size_t)dim * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return 0;
   };
   return lanczos_loop(c, dim, z_dev, factor, tol, max_iter, max_rows, step, result, iterations, products, status);
+}
+
+// ---- single steps, exported for the tests: each enqueues what one iteration of a loop above enqueues and returns ----------------
+int rmb_lanczos_step_device(rmb_ctx* c, int product, int in_plane, double* V_dev, long ldv, long i, double eta, double* x1_dev, double* col_dev,
+                            double* col_mapped_dev) {
+  if (int rc = check_ready(c)) return rc;
+  if (product != 0 && product != 1) return fail(RMB_ERR_ARG, "rmb_lanczos_step_device: product must be 0 (M_tt) or 1 (grand mobility)");
+  if (product == 1 && in_plane) return fail(RMB_ERR_ARG, "rmb_lanczos_step_device: the grand mobility has no in-plane variant");
+  if (c->tgt_begin != 0 || c->tgt_end != c->n) return fail(RMB_ERR_STATE, "rmb_lanczos_step_device: needs the full target range");
+  if (!V_dev || !x1_dev || !col_dev) return fail(RMB_ERR_ARG, "null pointer");
+  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
+  const long dim = (product == 1 ? 6 : 3) * c->n;
+  if (i < 0 || i + 1 > kCoefMax || ldv < dim) return fail(RMB_ERR_ARG, "rmb_lanczos_step_device: need 0 <= i <= 255 and ldv >= the vector length");
+  RMB_HIP(hipSetDevice(c->device));
+  return plain_lanczos_step(c, product, in_plane, V_dev, ldv, i, eta, x1_dev, col_dev, col_mapped_dev);
+}
+
+int rmb_krylov_lincomb_device(rmb_ctx* c, double* y_dev, const double* V_dev, long ldv, const double* coef_dev, long k, long n) {
+  if (!c) return fail(RMB_ERR_ARG, "null context");
+  if (k < 1 || k > kCoefMax || n < 1 || ldv < n) return fail(RMB_ERR_ARG, "rmb_krylov_lincomb_device: need 1 <= k <= 256, n >= 1, ldv >= n");
+  if (!y_dev || !V_dev || !coef_dev) return fail(RMB_ERR_ARG, "null pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  return launch_lincomb(c, y_dev, V_dev, ldv, coef_dev, k, n);
+}
+
+int rmb_krylov_norm_device(rmb_ctx* c, const double* v_dev, long n, double* out_dev) {
+  if (!c) return fail(RMB_ERR_ARG, "null context");
+  if (n < 1) return fail(RMB_ERR_ARG, "rmb_krylov_norm_device: need n >= 1");
+  if (!v_dev || !out_dev) return fail(RMB_ERR_ARG, "null pointer");
+  RMB_HIP(hipSetDevice(c->device));
+  return launch_norm(c, v_dev, n, out_dev);
 }
 
 }  // extern "C"

@@ -213,6 +213,7 @@ struct rmb_ctx : rmbi::CtxBuffers {
   int ev_count = 0;  // events recorded since last reset (capped at ring size)
   long timing_launches = 0;  // sweeps seen since the last reset (sampling stride of the "timing" option)
   // last launch
+  long last_krylov_partials = 0;   // first-pass partials per basis row a finishing launch left for the last Gram-Schmidt step (0: its own dots launch ran)
   int last_path = 0;           // 0 = sweep, 1 = symmetric (per wave), 2 = deterministic symmetric, 3 = symmetric, workgroup-cooperative,
                                // 4 = symmetric, two target blobs per lane
   long last_tiles = 0, last_chunks = 0, last_wgs = 0;

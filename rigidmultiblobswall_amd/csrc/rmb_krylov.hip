@@ -172,10 +172,12 @@ __global__ __launch_bounds__(kKrT) void ortho_normalise_kernel(const OrthoArgs a
   if (a.col_host && blockIdx.x == 0)      // col[0..rows) was written by the launch before this one
     for (long r = threadIdx.x; r < a.rows; r += kKrT) a.col_host[r] = a.col[r];
   __syncthreads();
-  const double inv = 1.0 / nrm;      // |w| = 0 (exact breakdown): inf / nan in v_next, as w / |w| gives; the caller stops on col[rows] == 0
+  // v_next = w / |w| by a true division: correctly rounded, so an exactly representable quotient comes out exact (w times the
+  // rounded reciprocal is off by an ulp already for 3 / 5).  |w| = 0 (exact breakdown): inf / nan in v_next; the caller stops
+  // on col[rows] == 0
   const long base = blockIdx.x * a.chunk;
   const long len = (a.n - base) < a.chunk ? (a.n - base) : a.chunk;
-  for (long e = threadIdx.x; e < len; e += kKrT) a.v_next[base + e] = a.w[base + e] * inv;
+  for (long e = threadIdx.x; e < len; e += kKrT) a.v_next[base + e] = a.w[base + e] / nrm;
 }
 
 // The normalisation with the NEXT iteration's first launch fused in (rmb_rigid_gmres_device, rmb_rigid_lanczos_device):
@@ -207,11 +209,10 @@ __global__ __launch_bounds__(1024) void ortho_normalise_pc_kernel(const NormPcAr
   if (a.o.col_host && b == 0)
     for (long r = threadIdx.x; r < a.o.rows; r += blockDim.x) a.o.col_host[r] = a.o.col[r];
   __syncthreads();
-  const double inv = 1.0 / nrm;
   const long r1 = a.r1, rows = a.r1 + a.r2;
   for (long k = threadIdx.x; k < rows; k += blockDim.x) {
     const long e = k < r1 ? b * r1 + k : a.n_top + a.r2 * b + (k - r1);
-    const double v = a.o.w[e] * inv;
+    const double v = a.o.w[e] / nrm;
     a.o.v_next[e] = v;
     xl[k] = v;
   }
@@ -275,13 +276,12 @@ __global__ __launch_bounds__(kKrT) void ortho_last_kernel(const OrthoArgs a) {
   __syncthreads();
   const double nrm = low_sync_norm(a, hl, &nrm_s);
   if (blockIdx.x == 0) low_sync_column(a, hl, nrm);
-  const double inv = 1.0 / nrm;
   const long base = blockIdx.x * a.chunk;
   const long len = (a.n - base) < a.chunk ? (a.n - base) : a.chunk;
   for (long e = threadIdx.x; e < len; e += kKrT) {
     const double w2 = second_update(a, hl, base + e);
     a.w[base + e] = w2;
-    a.v_next[base + e] = w2 * inv;
+    a.v_next[base + e] = w2 / nrm;
   }
 }
 
@@ -295,12 +295,11 @@ __global__ __launch_bounds__(1024) void ortho_last_pc_kernel(const NormPcArgs a)
   __syncthreads();
   const double nrm = low_sync_norm(a.o, hl, &nrm_s);
   if (b == 0) low_sync_column(a.o, hl, nrm);
-  const double inv = 1.0 / nrm;
   for (long k = threadIdx.x; k < rws; k += blockDim.x) {
     const long e = k < r1 ? b * r1 + k : a.n_top + a.r2 * b + (k - r1);
     const double w2 = second_update(a.o, hl, e);
     a.o.w[e] = w2;
-    const double v = w2 * inv;
+    const double v = w2 / nrm;
     a.o.v_next[e] = v;
     xl[k] = v;
   }
@@ -355,6 +354,21 @@ int rmb_krylov_orthogonalize2_device(rmb_ctx* c, long n, long rows, const double
   return krylov_orthogonalize_impl(c, n, rows, V_dev, ldv, w_dev, col_dev, v_next_dev, col_mapped_dev, nullptr);
 }
 
+int rmb_krylov_orthogonalize3_device(rmb_ctx* c, long n, long rows, const double* V_dev, long ldv, double* w_dev, double* col_dev,
+                                     double* v_next_dev, double* col_mapped_dev, int low_sync, long n_bodies, long r1, long r2,
+                                     const rmb_block* a11, const rmb_block* a12, const rmb_block* a21, const rmb_block* a22, double* z_dev) {
+  if (!z_dev) return krylov_orthogonalize_impl(c, n, rows, V_dev, ldv, w_dev, col_dev, v_next_dev, col_mapped_dev, nullptr, 0, low_sync != 0);
+  // (checked here, before the first launch: krylov_orthogonalize_impl looks at the blocks only when it reaches the last one)
+  if (n_bodies < 1 || r1 < 0 || r2 < 0 || r1 + r2 < 1 || n_bodies * (r1 + r2) != n)
+    return fail(RMB_ERR_ARG, "rmb_krylov_orthogonalize3_device: need n_bodies >= 1, r1, r2 >= 0 and n_bodies (r1 + r2) = n");
+  // (dynamic LDS of the last launch: the slices, their row sums and up to kKrMaxRows coefficients; 64 bytes for its static scalars)
+  if ((size_t)(2 * (r1 + r2) + kKrMaxRows) * sizeof(double) + 64 > 64 * 1024)
+    return fail(RMB_ERR_ARG, "rmb_krylov_orthogonalize3_device: r1 + r2 above 3964 (a body's slices and row sums are kept in LDS)");
+  auto ref = [](const rmb_block* b) { return b && b->p ? BlockRef{b->p, b->batch_stride, b->row_stride, b->col_stride} : BlockRef{nullptr, 0, 0, 0}; };
+  const PcBlocks pc{n_bodies, r1, r2, ref(a11), ref(a12), ref(a21), ref(a22), z_dev};
+  return krylov_orthogonalize_impl(c, n, rows, V_dev, ldv, w_dev, col_dev, v_next_dev, col_mapped_dev, &pc, 0, low_sync != 0);
+}
+
 }  // extern "C"
 
 namespace rmbi {
@@ -407,6 +421,7 @@ int krylov_orthogonalize_impl(rmb_ctx* c, long n, long rows, const double* V_dev
   a.n_part1 = a.n_chunks;
   a.low_sync = low_sync && c->opt_krylov_low_sync ? 1 : 0;
   if (part1_bodies > 0) { a.part1 = a.h1 + kKrMaxRows; a.n_part1 = part1_bodies; }       // krylov_body_partials' buffer
+  c->last_krylov_partials = part1_bodies;
   const dim3 grid((unsigned)a.n_chunks), block(kKrT);
   const size_t lds_w = (size_t)chunk * sizeof(double), lds_wh = lds_w + (size_t)rows * sizeof(double);
   if (part1_bodies == 0) hipLaunchKernelGGL(ortho_dots_kernel, grid, block, lds_w, c->stream, a);

@@ -692,6 +692,9 @@ int arnoldi_step_impl(rmb_ctx* c, long n_bodies, long n_b, const double* A11_dev
                       double* col_dev, double* col_mapped_dev, bool z_ready, bool fuse_pc) {
   if (int rc = check_ready(c)) return rc;
   if (n_bodies < 1 || n_b < 1 || j < 0) return fail(RMB_ERR_ARG, "rmb_rigid_arnoldi_step_device: bad n_bodies / n_b / j");
+  // (before the first launch: the block product below writes 3 n_bodies n_b + 6 n_bodies doubles of z)
+  if (n_bodies * n_b != c->n) return fail(RMB_ERR_STATE, "rmb_rigid_arnoldi_step_device: the resident configuration does not hold n_bodies x n_b blobs");
+  if (!(eta > 0.0)) return fail(RMB_ERR_ARG, "eta must be positive");
   if (!A11_dev || !A12_dev || !A21_dev || !A22_dev || !K_dev || !V_dev || !z_dev || !w_dev || !col_dev) return fail(RMB_ERR_ARG, "null pointer");
   const long nn = 3 * n_b, n3 = 3 * n_bodies * n_b, n = n3 + 6 * n_bodies;
   if (ldv < n) return fail(RMB_ERR_ARG, "rmb_rigid_arnoldi_step_device: ldv < 3 N + 6 n_bodies");
@@ -836,6 +839,22 @@ int rmb_rigid_arnoldi_step_device(rmb_ctx* c, long n_bodies, long n_b, const dou
                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev) {
   return arnoldi_step_impl(c, n_bodies, n_b, A11_dev, A12_dev, A21_dev, A22_dev, K_dev, V_dev, ldv, j, eta, z_dev, w_dev, col_dev,
                            col_mapped_dev, false, false);
+}
+
+// The same step in the forms the native loop runs (rmb_rigid_gmres_device): z_ready, fuse_pc as arnoldi_step_impl takes them.
+int rmb_rigid_arnoldi_step2_device(rmb_ctx* c, long n_bodies, long n_b, const double* A11_dev, const double* A12_dev,
+                                   const double* A21_dev, const double* A22_dev, const double* K_dev, double* V_dev, long ldv, long j,
+                                   double eta, double* z_dev, double* w_dev, double* col_dev, double* col_mapped_dev, int z_ready, int fuse_pc) {
+  return arnoldi_step_impl(c, n_bodies, n_b, A11_dev, A12_dev, A21_dev, A22_dev, K_dev, V_dev, ldv, j, eta, z_dev, w_dev, col_dev,
+                           col_mapped_dev, z_ready != 0, fuse_pc != 0);
+}
+
+// One step of rmb_rigid_lanczos_device's loop: pv_ready, fuse_next as lanczos_step_impl takes them.
+int rmb_rigid_lanczos_step_device(rmb_ctx* c, long n_bodies, long n_b, const double* Linv_dev, double* V_dev, long ldv, long i, double eta,
+                                  double* pv_dev, double* mw_dev, double* d_dev, double* col_dev, double* col_mapped_dev, int pv_ready,
+                                  int fuse_next) {
+  return lanczos_step_impl(c, n_bodies, n_b, Linv_dev, V_dev, ldv, i, eta, pv_dev, mw_dev, d_dev, col_dev, col_mapped_dev, pv_ready != 0,
+                           fuse_next != 0);
 }
 
 }  // extern "C"
